@@ -2,7 +2,7 @@
 """Headline benchmark: img/s of forward + backward of the full OneFormer model with a Swin-L backbone
 on synthetic 1024x2048 batches, 2 images per GPU, data-parallel over N GPUs of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,11 +12,16 @@ forward of backbone + pixel decoder + transformer decoder + the final x4 mask up
 backward, and (N > 1) the bucketed RCCL gradient all-reduce.  Rank 0 prints ONE JSON line.
 The timed region is bracketed by barrier + torch.cuda.synchronize() on both sides; the reported time
 is the MAX over ranks; `value` = images all ranks processed / that time.  The headline runs the model in eval() mode
-(deterministic, the full FLOPs of every residual branch); the training-mode step (DropPath / dropout on) is timed as
-well and reported under `train_mode`.
+(deterministic, the full FLOPs of every residual branch); with --full the training-mode step (DropPath / dropout on) is
+timed as well and reported under `train_mode`.
 
-Extra keys of the line (all measured in this run; rank 0, N = 1 only, after the timed region):
+A plain run sets up, warms up, times the K steps and prints the line; every other measurement below runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (_dump_outputs) as DIR/<name>.npy, after the timed region.
+
+Extra keys of the line (all measured in this run):
   `step_ms`            per-iteration device time of the timed steps (HIP events): median / min / max
+With --full, after the timed region (rank 0; forward_only, train_mode, gpu_eager_baseline and cpu_baseline with N = 1 only,
+--no-extras skipping the first three and --no-cpu-baseline the last):
   `host_enqueue_ms`    host time to enqueue one step from an idle stream (launch-bound if >= ms_per_step)
   `forward_only`       inference forward (no_grad, incl. the mask upsample) img/s
   `train_mode`         the same step with model.train(): stochastic depth + the decoders' dropout active
@@ -25,7 +30,7 @@ Extra keys of the line (all measured in this run; rank 0, N = 1 only, after the 
   `roofline`           dominant kernel family (bf16 MFMA GEMM) timed per launch with HIP events on its launch stream
                        (`uenc_prof_*`) over a repetition of the timed steps; algorithmic FLOPs = 2*M*N*K per launch;
                        per-family algorithmic bytes; `traffic` from the committed rocprofv3 PMC summary when it was
-                       measured on the current kernel sources (else null)
+                       measured on the current kernel sources (else null); `mfma_util` likewise from the committed PMC summary
   `cpu_baseline`       the fp32 oracle (a "port") on the host cores: forward+backward of ONE full-size 1024x2048 image, two samples;
                        `c0` = BASELINE configs[0] (Swin-T, 1 x 512 x 1024, forward, 1 warm-up + 3 timed)
 """
@@ -287,6 +292,48 @@ def _self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_SAMPLE = 1 << 20             # elements kept of a larger output (a fixed, seeded sample); aux masks keep a quarter of that
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(outdir, loss, out, masks_up, model):
+    """What the last timed step handed its caller, as float32 / float64 .npy files: the loss, the predictions of the final and
+    the nine auxiliary decoder layers, the x4-upsampled masks, and the parameter gradients (the norm of every parameter's gradient
+    in named_parameters() order, and a sample of all of them concatenated in that order).  Tensors above DUMP_SAMPLE elements are
+    sampled at indices drawn from a generator seeded by the file name, so that the same arguments give the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+
+    def sample(name, t, k=DUMP_SAMPLE):
+        t = t.detach()
+        if t.numel() > k:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (k,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        return t.float()
+
+    arrs = {"loss": loss.detach().double().reshape(1)}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrs[k] = sample(k, v)
+    for i, aux in enumerate(out.get("aux_outputs", [])):
+        for k, v in aux.items():
+            if torch.is_tensor(v):
+                arrs[f"aux{i}_{k}"] = sample(f"aux{i}_{k}", v, DUMP_SAMPLE // 4)
+    arrs["pred_masks_upsampled"] = sample("pred_masks_upsampled", masks_up)
+    params = [p for _, p in model.named_parameters()]
+    arrs["grad_norms"] = torch.stack([p.grad.detach().double().norm() if p.grad is not None else
+                                      torch.zeros((), dtype=torch.float64, device=p.device) for p in params])
+    arrs["grads"] = sample("grads", torch.cat([p.grad.detach().reshape(-1) if p.grad is not None else
+                                               torch.zeros(p.numel(), device=p.device) for p in params]))
+    total = sum(v.numel() * v.element_size() for v in arrs.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for k, v in arrs.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.cpu().numpy())
+    print(f"[bench] --dump-outputs: {len(arrs)} arrays, {total / 2 ** 20:.1f} MiB in {outdir}", file=sys.stderr, flush=True)
+
+
 def _rendezvous_only(args, world, rank):
     """Plumbing check of the N > 1 entry (CPU test, gloo): rendezvous, barrier, the MAX-over-ranks reduction of the timed region,
     rank 0's JSON line -- no model, no GPU, `value` null."""
@@ -307,8 +354,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip forward-only / train-mode / eager-baseline legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure host enqueue time, the per-launch GEMM roofline, the forward-only / train-mode / "
+                         "eager-GPU legs and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, samples of the large tensors)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip forward-only / train-mode / eager-baseline legs (profiling runs)")
     ap.add_argument("--bucket-mb", type=float, default=64.0)
     ap.add_argument("--check-dp", default="", help="N > 1: verify the reduced gradients against single-rank passes, write this JSON")
     ap.add_argument("--rendezvous-only", action="store_true", help="N ranks rendezvous over gloo and print the line's skeleton (CPU plumbing test)")
@@ -316,6 +368,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))          # never report dp1 for --gpus N: start the ranks, or fail with the child's code
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -366,12 +420,17 @@ def main():
                 for _ in range(PER_GPU_BATCH)]
     batch = make_batch(rank)
 
-    def step(b=None):
+    kept = {}
+
+    def step(b=None, keep=False):
         buckets.zero_grad()
         ops.begin_step(fresh_grads=True)       # weights change every training step: every bf16 operand copy is re-cast; grads are zero
         out, images = model.forward_features(b if b is not None else batch)
         with torch.no_grad():                  # reference :255-263, part of the forward it times
-            model.upsample_masks(out["pred_masks"], images.tensor.shape[-2:])
+            up = model.upsample_masks(out["pred_masks"], images.tensor.shape[-2:])
+        if keep:                               # --dump-outputs: the last timed step's results stay alive past the timed region
+            kept.update(out=out, masks_up=up)
+        del up                                 # otherwise released before loss and backward, as it always was
         loss = synthetic_loss(out)
         loss.backward()
         buckets.finish()
@@ -389,44 +448,47 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         evs[i][0].record()
-        loss = step()
+        loss = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         evs[i][1].record()
     sync()
     dt = time.perf_counter() - t0
     loss_val = float(loss.detach())
     step_ms = [a.elapsed_time(b) for a, b in evs]
-    # host cost of one step, enqueued into an idle stream (the GPU is behind the host for the whole call)
-    t1 = time.perf_counter()
-    step()
-    host_ms = (time.perf_counter() - t1) * 1e3
-    sync()
-    # per-launch timing of the GEMM families: HIP events recorded on the launch stream around every launch, over a repetition
-    # of the same K steps -- inside the timed region the ~1200 event pairs per step cost 4 % of `value` (measured: 23.4 vs
-    # 24.4 img/s), so the timed region itself stays un-instrumented
-    capi.lib.uenc_prof_enable(1)
-    for _ in range(args.steps):
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, kept["out"], kept["masks_up"], model)
+    kept.clear()
+    host_ms, fams, alg_bytes = None, {}, {}
+    if args.full:
+        # host cost of one step, enqueued into an idle stream (the GPU is behind the host for the whole call)
+        t1 = time.perf_counter()
         step()
-    sync()
+        host_ms = (time.perf_counter() - t1) * 1e3
+        sync()
+        # per-launch timing of the GEMM families: HIP events recorded on the launch stream around every launch, over a repetition
+        # of the same K steps -- inside the timed region the ~1200 event pairs per step cost 4 % of `value` (measured: 23.4 vs
+        # 24.4 img/s), so the timed region itself stays un-instrumented
+        capi.lib.uenc_prof_enable(1)
+        for _ in range(args.steps):
+            step()
+        sync()
+        for kind, name in ((4, "gemm_nt256_kernel"), (5, "gemm_nt128_kernel"), (0, "gemm_nt_kernel"), (1, "gemm_tn*_kernel")):
+            ms, fl, n, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_long(), ctypes.c_double()
+            capi.lib.uenc_prof_collect(kind, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(n))
+            capi.lib.uenc_prof_collect_bytes(kind, ctypes.byref(by))
+            fams[name] = (ms.value, fl.value, n.value)
+            alg_bytes[name] = by.value
+        capi.lib.uenc_prof_enable(0)
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if dist.is_initialized():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
-
-    fams, alg_bytes = {}, {}
-    for kind, name in ((4, "gemm_nt256_kernel"), (5, "gemm_nt128_kernel"), (0, "gemm_nt_kernel"), (1, "gemm_tn*_kernel")):
-        ms, fl, n, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_long(), ctypes.c_double()
-        capi.lib.uenc_prof_collect(kind, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(n))
-        capi.lib.uenc_prof_collect_bytes(kind, ctypes.byref(by))
-        fams[name] = (ms.value, fl.value, n.value)
-        alg_bytes[name] = by.value
-    capi.lib.uenc_prof_enable(0)
 
     dp_rec = None
     if world > 1 and args.check_dp:
         dp_rec = dp_check(model, buckets, [make_batch(r) for r in range(world)], step, rank, world, device)
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         # forward only (inference): no_grad, incl. the x4 mask upsample
         def fwd():
             with torch.no_grad():
@@ -470,21 +532,6 @@ def main():
 
     if rank == 0:
         imgs = PER_GPU_BATCH * world * args.steps
-        dom = max(fams, key=lambda k: fams[k][0])
-        ms, fl, n = fams[dom]
-        achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        gemm_ms = sum(v[0] for v in fams.values())
-        # L2 <-> fabric bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process; the committed
-        # summary of the two rocprofv3 --pmc passes of this same command (tools/pmc_traffic.py) is quoted when it matches the sources
-        traffic, traffic_src = None, None
-        pmc = _quoted_profile("pmc_traffic")
-        if pmc is not None:
-            try:
-                traffic = pmc["families"][dom]["traffic_bytes_per_launch"]
-                traffic_src = f"profiles/{PROFILE_ROUND}_pmc_traffic.json (rocprofv3 PMC passes at {pmc.get('git_head', '?')}, kernel sources {pmc['kernel_sources_sha']})"
-            except Exception:
-                pass
-        mf = _quoted_profile("mfma_util")
         swin = BACKBONE != "dinat"
         rec = {
             "metric": "img/s fwd+bwd Swin-L 1024x2048 bs=2 per GPU" if swin else "img/s fwd+bwd DiNAT-L 1024x2048 bs=2 per GPU",
@@ -495,27 +542,43 @@ def main():
                                     "150-query masked-attention decoder), 1024x2048, fwd+bwd, synthetic loss") if swin else
                                    ("BASELINE configs[4]: full OneFormer with the DiNAT-L backbone (neighbourhood attention, kernel 7), "
                                     "1024x2048, fwd+bwd, synthetic loss [UENC_BENCH_BACKBONE=dinat]"),
-                       "global_batch": PER_GPU_BATCH * world, "parallelism": f"dp{world}", "mode": "train()" if os.environ.get("UENC_BENCH_TRAIN") == "1" else "eval() (train_mode reported separately)"},
+                       "global_batch": PER_GPU_BATCH * world, "parallelism": f"dp{world}", "mode": "train()" if os.environ.get("UENC_BENCH_TRAIN") == "1" else "eval() (train_mode reported separately with --full)"},
             "step_ms": {"median": round(statistics.median(step_ms), 3), "min": round(min(step_ms), 3), "max": round(max(step_ms), 3)},
-            "host_enqueue_ms": round(host_ms, 2),
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1), "peak": 2500.0, "unit": "TFLOP/s",
-                         "frac": round(achieved / 2500.0, 4), "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": round(alg_bytes[dom] / max(n, 1)), "launches_per_step": n // max(args.steps, 1),
-                         "avg_launch_us": round(ms * 1e3 / max(n, 1), 2),
-                         "gemm_share_of_step": round(gemm_ms / (dt * 1e3), 3),
-                         "families": {k: {"tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 else 0.0,
-                                          "ms_per_step": round(v[0] / max(args.steps, 1), 2), "launches_per_step": v[2] // max(args.steps, 1),
-                                          "algorithmic_bytes_per_step": round(alg_bytes[k] / max(args.steps, 1)),
-                                          "algorithmic_gbps": round(alg_bytes[k] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0}
-                                      for k, v in fams.items()}},
             "loss": round(loss_val, 5),
         }
+        if args.full:
+            dom = max(fams, key=lambda k: fams[k][0])
+            ms, fl, n = fams[dom]
+            achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            gemm_ms = sum(v[0] for v in fams.values())
+            # L2 <-> fabric bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process; the committed
+            # summary of the two rocprofv3 --pmc passes of this same command (tools/pmc_traffic.py) is quoted when it matches the sources
+            traffic, traffic_src = None, None
+            pmc = _quoted_profile("pmc_traffic")
+            if pmc is not None:
+                try:
+                    traffic = pmc["families"][dom]["traffic_bytes_per_launch"]
+                    traffic_src = f"profiles/{PROFILE_ROUND}_pmc_traffic.json (rocprofv3 PMC passes at {pmc.get('git_head', '?')}, kernel sources {pmc['kernel_sources_sha']})"
+                except Exception:
+                    pass
+            rec["host_enqueue_ms"] = round(host_ms, 2)
+            rec["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1), "peak": 2500.0, "unit": "TFLOP/s",
+                               "frac": round(achieved / 2500.0, 4), "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": round(alg_bytes[dom] / max(n, 1)), "launches_per_step": n // max(args.steps, 1),
+                               "avg_launch_us": round(ms * 1e3 / max(n, 1), 2),
+                               "gemm_share_of_step": round(gemm_ms / (dt * 1e3), 3),
+                               "families": {k: {"tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 else 0.0,
+                                                "ms_per_step": round(v[0] / max(args.steps, 1), 2), "launches_per_step": v[2] // max(args.steps, 1),
+                                                "algorithmic_bytes_per_step": round(alg_bytes[k] / max(args.steps, 1)),
+                                                "algorithmic_gbps": round(alg_bytes[k] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0}
+                                            for k, v in fams.items()}}
         if force_coll:
             rec["config"]["rccl_rehearsal"] = ("UENC_DP_FORCE_COLLECTIVE=1: every gradient bucket went through an RCCL all-reduce (ncclAvg, async) "
                                                "in a world of one rank -- the N > 1 call path on one GPU; not a scaling figure")
         if swin:
             rec["config"]["model_tflop_per_step_per_gpu"] = round(3 * GFLOP_FWD_PER_IMG * PER_GPU_BATCH / 1e3, 2)
             rec["model_tflops_per_gpu"] = round(3 * GFLOP_FWD_PER_IMG * PER_GPU_BATCH / 1e3 / (dt / args.steps), 1)
+        mf = _quoted_profile("mfma_util") if args.full else None
         if mf is not None:
             rec["mfma_util"] = {k: mf[k] for k in ("mfma_busy_frac_of_step", "mfma_busy_frac_of_gpu_busy", "source") if k in mf}
         rec.update(extras)
@@ -523,7 +586,7 @@ def main():
             rec["dp_check"] = dp_rec
             with open(args.check_dp, "w") as f:
                 json.dump(dp_rec, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline()
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():

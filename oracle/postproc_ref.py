@@ -3,8 +3,8 @@
 TEST INFRASTRUCTURE: only `tests/` imports it.  Parity status: PINNED -- `oracle/make_postproc_golden.py` calls the reference's
 own `OneFormer.semantic_inference` / `panoptic_inference` / `instance_inference` (model/oneformer_model.py:367-489, loaded through
 `oracle/ref_loader.load_meta_arch`) and the documented `sem_seg_postprocess` on synthetic predictions and commits inputs +
-outputs as `tests/golden/postproc.npz`; `tests/test_postproc_cpu.py` checks this file against them (and live against the
-reference where /root/reference exists).  Citations are relative to /root/reference/model/oneformer_model.py.
+outputs as `tests/golden/postproc.npz`; `tests/test_postproc_cpu.py` checks this file against them (and against two more
+prediction sets in `tests/golden/oracle_vs_reference.npz`).  Citations are relative to the reference's model/oneformer_model.py.
 """
 from typing import Dict, List, Sequence, Tuple
 

@@ -6,7 +6,8 @@ and the `cpu_baseline` leg of `bench.py` may import it.  The shipped product
 
 Parity status: PINNED.  Every function below is checked in the build container
 against the reference's own modules imported from /root/reference
-(`oracle/ref_loader.py`, `tests/test_oracle_vs_reference.py`) and against the
+(`oracle/ref_loader.py`; `oracle/make_reference_golden.py` records the cases of
+`tests/test_oracle_vs_reference.py`) and against the
 fixtures those modules produced (`tests/golden/*.npz`, made by
 `oracle/make_golden.py`).  The reference holds no tests or golden vectors of its
 own.

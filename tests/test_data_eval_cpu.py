@@ -238,20 +238,23 @@ def test_inference_on_dataset_matches_the_reference(caplog):
     assert [blank(r.message) for r in caplog.records] == [blank(s) for s in want["log_lines"]]
 
 
-def test_dataset_registration_matches_the_reference(tmp_path):
+def test_dataset_registration_matches_the_reference(tmp_path, monkeypatch):
     """Cityscapes panoptic and KITTI sequence dataset dicts from synthetic trees, and the registered names / metadata, against what the
     reference's register_cityscapes_panoptic.py / register_kitti.py produced on the same trees."""
     from oracle.data_eval_inputs import make_cityscapes_tree, make_kitti_tree
     from uenc import datasets as DS
     from uenc.data import DatasetCatalog, MetadataCatalog
     _, meta = _fixture()
-    croot = str(tmp_path / "cs")
+    # the trees live under a relative, dot-free root: the loader derives sem_seg_file_name with `path.split(".")[0]`, as the reference
+    # does (register_cityscapes_panoptic.py:93), which a dot anywhere in the temporary directory's absolute path would cut short
+    monkeypatch.chdir(tmp_path)
+    croot = "cs"
     image_dir, gt_dir, gt_json = make_cityscapes_tree(croot)
     dicts = DS.load_cityscapes_panoptic(image_dir, gt_dir, gt_json, DS.cityscapes_panoptic_meta())
     rel = lambda d, root: {k: (os.path.relpath(v, root) if isinstance(v, str) and v.startswith(root) else v) for k, v in d.items()}
     assert [rel(d, croot) for d in dicts] == meta["cityscapes_dicts"]
     assert {d["type"] for d in dicts} == {"segmentation"} and dicts[0]["segments_info"][1]["category_id"] == 13        # car: label id 26 -> train id 13
-    kroot = str(tmp_path / "kitti")
+    kroot = "kitti"
     data_root, files_list = make_kitti_tree(kroot)
     kd = DS.load_kitti_sequence(data_root, files_list, ".jpg")
     assert [rel(d, kroot) for d in kd] == meta["kitti_dicts"]

@@ -143,7 +143,9 @@ def _diverging_worker(rank, world, port, q):
     torch.manual_seed(rank)                                   # different initial weights per rank: must be overwritten by rank 0's
     m = nn.Sequential(nn.Linear(4, 4), nn.Linear(4, 4))
     gb = GradBuckets(m, listen_ops=False)
-    w0 = m[0].weight.detach().clone()
+    # a numpy copy, not a tensor: a CPU tensor crosses the queue as a file descriptor that only lives as long as this process,
+    # which may have exited by the time the parent unpickles it
+    w0 = m[0].weight.detach().clone().numpy()
     gb.zero_grad()
     y = m[0](torch.ones(2, 4))
     if rank == 0:
@@ -174,7 +176,7 @@ def test_replicas_are_broadcast_and_a_diverging_rank_is_caught():
             p.join(timeout=60)
             if p.is_alive():
                 p.terminate()
-    assert torch.equal(got[0][1], got[1][1])                  # parameters were broadcast from rank 0 at construction
+    assert torch.equal(torch.from_numpy(got[0][1]), torch.from_numpy(got[1][1]))     # parameters were broadcast from rank 0 at construction
     # BOTH ranks raise (the verdict is all-gathered): rank 0 must not carry on into a collective rank 1 never joins
     assert got[0][0] == "raised" and got[1][0] == "raised"
 

@@ -7,7 +7,9 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = "/root/reference/configs/cityscapes/swin/unified_encoder_cityscapes.yaml"
+# every key of the reference's shipped Swin-T config chain (configs/cityscapes/swin/unified_encoder_cityscapes.yaml and its `_BASE_`
+# files), resolved on the product's defaults by oracle/make_cfg_fixture.py
+REF_CFG_VALUES = os.path.join(ROOT, "tests", "golden", "cfg_cityscapes_swin_t.json")
 
 
 def _cfg():
@@ -45,12 +47,49 @@ def test_config_keys_and_overrides():
     assert cfg.MODEL.DEVICE == "cuda"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference configs not present")
-def test_reference_yaml_chain_builds_the_model():
+def _write_reference_chain(root):
+    """The resolved values of the reference's chain, written back as a three-file chain of the same form: a leaf one directory down
+    (swin/) with a relative `_BASE_: ../`, the Swin keys and SEG_MIN_SIZE_TRAIN as the reference's `!!python/object/apply:eval`
+    expression; a middle file with the other MODEL keys; a base file with everything else, and wrong values for keys that the files
+    above it override.  JSON flow mappings are YAML.  Returns the leaf's path and the flat values."""
+    import json
+    with open(REF_CFG_VALUES) as f:
+        flat = json.load(f)["cfg"]
+
+    def nest(items):
+        out = {}
+        for k, v in items:
+            node = out
+            for p in k.split(".")[:-1]:
+                node = node.setdefault(p, {})
+            node[k.split(".")[-1]] = v
+        return out
+    leaf = {k: v for k, v in flat.items() if k.startswith("MODEL.SWIN.")}
+    mid = {k: v for k, v in flat.items() if k.startswith("MODEL.") and k not in leaf}
+    base = {k: v for k, v in flat.items() if k not in leaf and k not in mid}
+    mid["MODEL.SWIN.EMBED_DIM"] = 1
+    base["INPUT.SEG_MIN_SIZE_TRAIN"] = [1]
+    base["MODEL.ONE_FORMER.NUM_OBJECT_QUERIES"] = 2
+    os.makedirs(os.path.join(root, "swin"))
+    with open(os.path.join(root, "base.yaml"), "w") as f:
+        f.write(json.dumps(nest(base.items())) + "\n")
+    with open(os.path.join(root, "mid.yaml"), "w") as f:
+        f.write(json.dumps({"_BASE_": "base.yaml", **nest(mid.items())}) + "\n")
+    path = os.path.join(root, "swin", "leaf.yaml")
+    with open(path, "w") as f:
+        f.write("_BASE_: ../mid.yaml\nMODEL: " + json.dumps(nest(leaf.items())["MODEL"]) + "\nINPUT:\n"
+                '  SEG_MIN_SIZE_TRAIN: !!python/object/apply:eval ["[int(x * 0.1 * 384) for x in range(5, 21)]"]\n')
+    return path, flat
+
+
+def test_reference_yaml_chain_builds_the_model(tmp_path):
     from oracle import torch_ref as T
+    from oracle.make_cfg_fixture import flatten
     from uenc.d2 import build_model
+    path, flat = _write_reference_chain(str(tmp_path))
     cfg = _cfg()
-    cfg.merge_from_file(REF_CFG)          # _BASE_ chain + the !!python/object/apply:eval tag
+    cfg.merge_from_file(path)             # _BASE_ chain + the !!python/object/apply:eval tag
+    assert flatten(cfg) == flat           # every key resolves to the reference chain's value
     assert cfg.INPUT.SEG_MIN_SIZE_TRAIN[0] == 192 and cfg.MODEL.ONE_FORMER.NUM_OBJECT_QUERIES == 150
     assert cfg.MODEL.SEM_SEG_HEAD.PIXEL_DECODER_NAME == "MSDeformAttnPixelDecoder"
     cfg.merge_from_list(["MODEL.DEVICE", "cpu"])

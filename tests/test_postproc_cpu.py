@@ -1,8 +1,8 @@
 """oracle/postproc_ref.py against the fixtures produced by the reference's own `semantic_inference` / `panoptic_inference`
-(tests/golden/postproc.npz, made by oracle/make_postproc_golden.py), and live against the reference where it is present."""
-import types
+(tests/golden/postproc.npz, made by oracle/make_postproc_golden.py, and tests/golden/oracle_vs_reference.npz, made by
+oracle/make_reference_golden.py)."""
+import json
 
-import pytest
 import torch
 
 from conftest import load_golden
@@ -34,17 +34,14 @@ def test_oracle_matches_reference_fixtures():
 
 
 def test_oracle_matches_reference_live():
-    from oracle import ref_loader
-    if not ref_loader.available():
-        pytest.skip("reference tree not present")
-    O = ref_loader.load_meta_arch().OneFormer
+    """Two more prediction sets through the reference's semantic / panoptic inference (object threshold 0.4, overlap 0.7, things 5
+    and 6), recorded by oracle/make_reference_golden.py in tests/golden/oracle_vs_reference.npz."""
+    g = load_golden("oracle_vs_reference")
+    infos = json.loads(bytes(g["meta_json"].numpy()).decode())["postproc_info"]
     for seed in (5, 6):
-        cls, masks = P.synthetic_predictions(14, 7, 12, 20, seed)
+        cls, masks = g[f"pp{seed}_cls"], g[f"pp{seed}_masks"]
         mp = P.upsample_and_crop(masks, (48, 80), (44, 80), (44, 80))
-        fake = types.SimpleNamespace(sem_seg_head=types.SimpleNamespace(num_classes=7), object_mask_threshold=0.4, overlap_threshold=0.7,
-                                     metadata=types.SimpleNamespace(thing_dataset_id_to_contiguous_id={5: 5, 6: 6}))
-        torch.testing.assert_close(P.semantic_inference(cls, mp), O.semantic_inference(fake, cls, mp), atol=1e-6, rtol=1e-6)
+        torch.testing.assert_close(P.semantic_inference(cls, mp), g[f"pp{seed}_sem"], atol=1e-6, rtol=1e-6)
         seg, info = P.panoptic_inference(cls, mp, 7, 0.4, 0.7, [5, 6])
-        seg2, info2 = O.panoptic_inference(fake, cls, mp)
-        assert torch.equal(seg, seg2) and info == info2
+        assert torch.equal(seg, g[f"pp{seed}_pan"]) and info == infos[str(seed)]
 

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=gpurun_out
 rm -rf $R/pmc_lds
-timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $R/pmc_lds -o l -- python3 bench.py --steps 1 --warmup 1 --no-extras --no-cpu-baseline > $R/pmc_lds.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $R/pmc_lds -o l -- python3 bench.py --full --steps 1 --warmup 1 --no-extras --no-cpu-baseline > $R/pmc_lds.log 2>&1 || exit 1
 python3 - <<'PY'
 import csv, collections, re, glob
 f = glob.glob('gpurun_out/pmc_lds/**/l_counter_collection.csv', recursive=True)[0]

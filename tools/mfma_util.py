@@ -1,7 +1,7 @@
 """MFMA utilisation of one bench step from a rocprofv3 PMC pass:
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d gpurun_out/pmc_mfma -o m -- \
-        python3 bench.py --steps 1 --warmup 1 --no-extras --no-cpu-baseline
+        python3 bench.py --full --steps 1 --warmup 1 --no-extras --no-cpu-baseline
     python tools/mfma_util.py gpurun_out/pmc_mfma/m_counter_collection.csv profiles/r02_mfma_util.json
 
 MfmaUtil (rocprofiler-sdk counter_defs.yaml, gfx950) = sum(SQ_VALU_MFMA_BUSY_CYCLES) / (max(GRBM_GUI_ACTIVE) * SIMD_NUM) * 100 with
@@ -45,7 +45,7 @@ if __name__ == "__main__":
         f = re.sub(r"<.*", "", name[i])
         fam[f][0] += c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0); fam[f][1] += c.get("GRBM_GUI_ACTIVE", 0.0) / 8.0; fam[f][2] += 1
     mf = sum(v[0] for v in fam.values()); act = sum(v[1] for v in fam.values())
-    out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE of bench.py --steps 1 --warmup 1 --no-extras --no-cpu-baseline (one full step)",
+    out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE of bench.py --full --steps 1 --warmup 1 --no-extras --no-cpu-baseline (one full step)",
            "formula": "sum(SQ_VALU_MFMA_BUSY_CYCLES) / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs)", "git_head": git_head(), "kernel_sources_sha": sources_sha(),
            "mfma_busy_frac_of_gpu_busy": round(mf / (act * 1024.0), 4), "dispatches": len(seg),
            "families": {f: {"launches": v[2], "mfma_util": round(v[0] / (v[1] * 1024.0), 4) if v[1] else 0.0, "share_of_active_cycles": round(v[1] / act, 4)}

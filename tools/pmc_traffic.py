@@ -1,8 +1,8 @@
 """HBM-side traffic per kernel family from two rocprofv3 PMC passes of bench.py (FETCH_SIZE and WRITE_SIZE, separate runs):
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o f -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o w -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch/f_counter_collection.csv gpurun_out/pmc_write/w_counter_collection.csv profiles/r02_pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_fetch -o f -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/pmc_write -o w -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+    python tools/pmc_traffic.py out/pmc_fetch/f_counter_collection.csv out/pmc_write/w_counter_collection.csv profiles/r02_pmc_traffic.json
 
 Units and corrections as MI355X_MICROARCH.md "HBM" prescribes: the counters are in KiB; on gfx950 FETCH_SIZE reports half the
 bytes of wide coalesced streaming reads (doubled here); WRITE_SIZE is exact for 16-byte streaming stores and float atomics.
@@ -32,6 +32,6 @@ for f, d in sorted(fam.items(), key=lambda x: -(x[1]["fetch_bytes"] + x[1]["writ
     out[f] = {k: (round(v) if isinstance(v, float) else v) for k, v in d.items()}
     print(f"{f[:44]:44s} launches {d['launches']:5d}  fetch {d['fetch_bytes']/1e9:8.2f} GB  write {d['write_bytes']/1e9:8.2f} GB  per launch {d['traffic_bytes_per_launch']/1e6:8.1f} MB")
 if len(sys.argv) > 3:
-    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of bench.py --steps 1 --warmup 1; FETCH_SIZE x2 (gfx950)",
+    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of bench.py --full --steps 1 --warmup 1; FETCH_SIZE x2 (gfx950)",
                "git_head": git_head(), "kernel_sources_sha": sources_sha(),       # bench.py quotes this file only while the kernel sources are unchanged
                "families": out}, open(sys.argv[3], "w"), indent=1)
