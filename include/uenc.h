@@ -353,7 +353,7 @@ int uenc_postproc_panoptic_label(const float* mask_logits, const int* ids, const
 /* ---- fp32 "exact" arithmetic mode (csrc/exact.hip; UENC_EXACT=1 / uenc.ops.set_exact) -----------------------------------
  * The reference computes in fp32 end to end (AMP off, configs/cityscapes/swin/unified_encoder_cityscapes.yaml:27-28; the pixel
  * decoder forces fp32, pixel_decoder/msdeformattn.py:336,343).  These entry points run the contractions of the path on fp32
- * operands with fp32 accumulation (v_mfma_f32_16x16x4_f32 for the GEMMs, VALU for the two attention cores), so that a
+ * operands with fp32 accumulation (v_mfma_f32_16x16x4_f32 for the GEMMs, VALU for the three attention cores), so that a
  * deviation from the reference can be split into bf16 rounding (the product's mode) and everything else (must be ~1e-5).
  * A verification mode: same call sites, same epilogues, no performance claim.
  *   gemm_nt_f32:  C = epi(alpha * (A W^T + bias)), all fp32, K % 4 == 0, lda / ldw % 4 == 0; aux / aux_out fp32 (the
@@ -363,7 +363,10 @@ int uenc_postproc_panoptic_label(const float* mask_logits, const int* ids, const
  *                 out / dout (B, H, W, C); same pad / shift / mask semantics as uenc_window_attn_* (model/modeling/backbone/
  *                 swin.py:250-289, :131-171, :414-440).  bwd: dqkv written, dtable and dbias_pad (3C) accumulated (atomics)
  *   mha_f32_{fwd,bwd}: the decoder's nn.MultiheadAttention cores, tensor contract of uenc_mha_* with fp32 tensors; lse (B, nH, Lq);
- *                 bwd: dq written, dk / dv (zeroed by the caller) accumulated, delta (B, nH, Lq) scratch */
+ *                 bwd: dq written, dk / dv (zeroed by the caller) accumulated, delta (B, nH, Lq) scratch
+ *   na2d_f32_{fwd,bwd}: DiNAT's neighbourhood attention, tensor contract and limits of uenc_na2d_* with fp32 tensors: qkv
+ *                 (B, H, W, 3, nH, 32), out / dout (B, H, W, nH, 32), rpb (nH, 2K-1, 2K-1) or NULL, lse (B, nH, H, W) (NULL
+ *                 allowed in the forward); bwd: dqkv written completely, drpb accumulated (atomics; may be NULL) */
 int uenc_gemm_nt_f32(const float* A, long lda, const float* W, long ldw, float* C, long ldc, int M, int N, int K, const float* bias,
                      int epilogue, const float* aux, long ldaux, float* aux_out, long ldaux_out, float alpha, int accumulate, uenc_stream_t stream);
 int uenc_gemm_tn_f32(const float* dY, long ldy, const float* X, long ldx, float* dW, long ldw, float* db, int M, int N, int K, uenc_stream_t stream);
@@ -378,6 +381,10 @@ int uenc_mha_f32_bwd(const float* q, long qs0, long qs1, const float* k, long ks
                      const uint8_t* mask, long mask_row_stride, const float* out, long os0, long os1, const float* lse, const float* dout,
                      long gos0, long gos1, float* dq, long dqs0, long dqs1, float* dk, long dks0, long dks1, float* dv, long dvs0, long dvs1,
                      float* delta, int B, int nH, int Lq, int S, float scale, float dropout_p, unsigned seed, uenc_stream_t stream);
+int uenc_na2d_f32_fwd(const float* qkv, const float* rpb, float* out, float* lse, int B, int H, int W, int nH, int K, int dilation,
+                      float scale, uenc_stream_t stream);
+int uenc_na2d_f32_bwd(const float* qkv, const float* rpb, const float* out, const float* dout, const float* lse, float* dqkv, float* drpb,
+                      int B, int H, int W, int nH, int K, int dilation, float scale, uenc_stream_t stream);
 
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */

@@ -4,7 +4,7 @@
 // activation handed from kernel to kernel and every accumulation in fp32, selected by UENC_EXACT=1 (uenc/ops.py): the mode
 // that shows what part of a deviation from the fp32 reference is bf16 rounding and what part would be a bug.  It is a
 // verification mode, built for correctness first: the GEMM runs on the fp32-input matrix instruction
-// v_mfma_f32_16x16x4_f32 (exact fp32 products and sums, 1/16 of the bf16 rate), the two attention cores are plain VALU
+// v_mfma_f32_16x16x4_f32 (exact fp32 products and sums, 1/16 of the bf16 rate), the three attention cores are plain VALU
 // kernels with per-lane online softmax.  Same C-ABI conventions as the rest of the library (include/uenc.h).
 //
 //   uenc_gemm_nt_f32          replaces the same ATen calls as uenc_gemm_nt (Linear / 1x1 conv / mask einsum, forward + dgrad)
@@ -12,7 +12,9 @@
 //   uenc_window_attn_f32_fwd  model/modeling/backbone/swin.py:250-289 around WindowAttention.forward :131-171
 //   uenc_window_attn_f32_bwd  its backward
 //   uenc_mha_f32_fwd / _bwd   the nn.MultiheadAttention cores of transformer_decoder/*.py (head_dim 32)
+//   uenc_na2d_f32_fwd / _bwd  DiNAT's neighbourhood attention (natten2dqkrpb + softmax + natten2dav), contract of uenc_na2d_*
 #include "common.h"
+#include "na2d.h"
 #include <math.h>
 
 enum { XEPI_NONE = 0, XEPI_GELU = 1, XEPI_RELU = 2, XEPI_RESIDUAL = 3, XEPI_MUL_DGELU = 4, XEPI_MUL_DRELU = 5 };
@@ -574,5 +576,171 @@ extern "C" int uenc_mha_f32_bwd(const float* q, long qs0, long qs1, const float*
     p.B = B; p.nH = nH; p.Lq = Lq; p.S = S; p.scale = scale;
     p.drop_thresh = attn_drop_thresh(dropout_p); p.seed = seed; p.inv_keep = 1.0f / (1.0f - dropout_p);
     hipLaunchKernelGGL(xmha_bwd_kernel, dim3((Lq + XQB - 1) / XQB, nH, B), dim3(256), 0, stream, p);
+    UENC_LAUNCH_RET();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// neighbourhood attention 2-D (DiNAT), fp32: the tensor contract of uenc_na2d_* (csrc/na2d.hip) with fp32 tensors, the window
+// of every query from axis_win (na2d.h, NATTEN's clamped window per residue class).  NATTEN's order: q * scale, then + rpb.
+// Forward: four lanes per (pixel, head), 8 channels each, 64 pixels of one image row per workgroup, per-lane online softmax.
+// ---------------------------------------------------------------------------------------------------------------------
+struct XNa {
+    const float* qkv; const float* rpb; float* out; float* lse;
+    const float* dout; float* dqkv; float* drpb;      // backward
+    int B, H, W, nH, K, d;
+    float scale;
+};
+
+__device__ __forceinline__ void xld8(const float* s, float (&v)[8]) {
+    const float4 a = *(const float4*)s, c = *(const float4*)(s + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+}
+
+__device__ __forceinline__ float xquad_sum(float v) {      // over the 4 lanes of one (pixel, head)
+    v += __shfl_xor(v, 1);
+    return v + __shfl_xor(v, 2);
+}
+
+// grid (ceil(W / 64), H, B * nH), block 256 = 64 pixels x 4 lanes
+__global__ __launch_bounds__(256) void xna_fwd_kernel(XNa p) {
+    const int h = blockIdx.z % p.nH, b = blockIdx.z / p.nH, y = blockIdx.y;
+    const int c8 = (threadIdx.x & 3) * 8;
+    const int xr = blockIdx.x * 64 + (threadIdx.x >> 2);
+    const int x = min(xr, p.W - 1);                 // tail lanes run a valid pixel (the quad shuffles stay defined), store nothing
+    const int C = p.nH * XHD, RB = 2 * p.K - 1;
+    const long pix = ((long)b * p.H + y) * p.W + x;
+    float q[8], acc[8];
+    xld8(p.qkv + pix * 3 * C + h * XHD + c8, q);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { q[c] *= p.scale; acc[c] = 0.f; }
+    const AxisWin wy = axis_win(y, p.H, p.d, p.K), wx = axis_win(x, p.W, p.d, p.K);
+    const float* rb = p.rpb != nullptr ? p.rpb + (long)h * RB * RB : nullptr;
+    float m = -INFINITY, l = 0.f;
+    for (int i = 0; i < p.K; ++i) {
+        const long krow = ((long)b * p.H + (wy.start + i) * p.d + wy.r) * p.W;
+        for (int j = 0; j < p.K; ++j) {
+            const float* kp = p.qkv + (krow + (wx.start + j) * p.d + wx.r) * 3 * C + C + h * XHD + c8;
+            float k[8], v[8];
+            xld8(kp, k);
+            xld8(kp + C, v);
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) s = fmaf(q[c], k[c], s);
+            s = xquad_sum(s);
+            if (rb != nullptr) s += rb[(wy.pb0 + i) * RB + wx.pb0 + j];
+            const float mn = fmaxf(m, s), cr = expf(m - mn), e = expf(s - mn);
+            l = l * cr + e;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = fmaf(e, v[c], acc[c] * cr);
+            m = mn;
+        }
+    }
+    if (xr >= p.W) return;
+    const float inv = 1.0f / l;
+    float* o = p.out + pix * C + h * XHD + c8;
+    *(float4*)o = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
+    *(float4*)(o + 4) = make_float4(acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv);
+    if (c8 == 0 && p.lse != nullptr) p.lse[(((long)b * p.nH + h) * p.H + y) * p.W + x] = m + logf(l);
+}
+
+// backward: one thread per query (pixel, head), all 32 channels.  It recomputes its probabilities from the saved log-sum-exp
+// (delta = dO . O from the forward's output), writes dq directly and adds its dk / dv contributions with global float atomics
+// (dqkv zeroed first by the entry point) and its rpb gradient into per-workgroup LDS bins, flushed with one global atomic per bin.
+// grid (ceil(W / 64), H, B * nH), block 64
+__global__ __launch_bounds__(64) void xna_bwd_kernel(XNa p) {
+    __shared__ float dbin[25 * 25];                 // (2K - 1)^2, K <= 13
+    const int RB = 2 * p.K - 1;
+    for (int i = threadIdx.x; i < RB * RB; i += 64) dbin[i] = 0.f;
+    __syncthreads();
+    const int h = blockIdx.z % p.nH, b = blockIdx.z / p.nH, y = blockIdx.y;
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    if (x < p.W) {
+        const int C = p.nH * XHD;
+        const long pix = ((long)b * p.H + y) * p.W + x;
+        float q[XHD], g[XHD], dq[XHD];
+        float delta = 0.f;
+        {
+            const float* qp = p.qkv + pix * 3 * C + h * XHD;
+            const float* gp = p.dout + pix * C + h * XHD;
+            const float* op = p.out + pix * C + h * XHD;
+#pragma unroll
+            for (int c = 0; c < XHD; c += 8) {
+                float o[8];
+                xld8(qp + c, *(float(*)[8])(q + c));
+                xld8(gp + c, *(float(*)[8])(g + c));
+                xld8(op + c, o);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { q[c + e] *= p.scale; dq[c + e] = 0.f; delta = fmaf(g[c + e], o[e], delta); }
+            }
+        }
+        const float lse = p.lse[(((long)b * p.nH + h) * p.H + y) * p.W + x];
+        const AxisWin wy = axis_win(y, p.H, p.d, p.K), wx = axis_win(x, p.W, p.d, p.K);
+        const float* rb = p.rpb != nullptr ? p.rpb + (long)h * RB * RB : nullptr;
+        for (int i = 0; i < p.K; ++i) {
+            const long krow = ((long)b * p.H + (wy.start + i) * p.d + wy.r) * p.W;
+            for (int j = 0; j < p.K; ++j) {
+                const long ko = (krow + (wx.start + j) * p.d + wx.r) * 3 * C + C + h * XHD;
+                float k[XHD], v[XHD];
+#pragma unroll
+                for (int c = 0; c < XHD; c += 8) {
+                    xld8(p.qkv + ko + c, *(float(*)[8])(k + c));
+                    xld8(p.qkv + ko + C + c, *(float(*)[8])(v + c));
+                }
+                const int bin = (wy.pb0 + i) * RB + wx.pb0 + j;
+                float s = 0.f, dp = 0.f;
+#pragma unroll
+                for (int c = 0; c < XHD; ++c) { s = fmaf(q[c], k[c], s); dp = fmaf(g[c], v[c], dp); }
+                if (rb != nullptr) s += rb[bin];
+                const float pr = expf(s - lse);
+                const float ds = pr * (dp - delta);         // d(score), also the rpb gradient of this (query, slot) pair
+                float* dk = p.dqkv + ko;
+#pragma unroll
+                for (int c = 0; c < XHD; ++c) {
+                    dq[c] = fmaf(ds, k[c], dq[c]);
+                    atomicAdd(dk + c, ds * q[c]);           // q already carries the scale: d(k) = scale * ds * q
+                    atomicAdd(dk + C + c, pr * g[c]);
+                }
+                if (p.drpb != nullptr) atomicAdd(&dbin[bin], ds);
+            }
+        }
+        float* o = p.dqkv + pix * 3 * C + h * XHD;
+#pragma unroll
+        for (int c = 0; c < XHD; c += 4) *(float4*)(o + c) = make_float4(dq[c] * p.scale, dq[c + 1] * p.scale, dq[c + 2] * p.scale, dq[c + 3] * p.scale);
+    }
+    if (p.drpb != nullptr) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < RB * RB; i += 64)
+            if (dbin[i] != 0.f) atomicAdd(p.drpb + (long)(blockIdx.z % p.nH) * RB * RB + i, dbin[i]);
+    }
+}
+
+static int xna_fill(XNa& p, int B, int H, int W, int nH, int K, int dilation, float scale) {
+    Na2d c = {};
+    c.B = B; c.H = H; c.W = W; c.nH = nH; c.d = dilation;
+    if (int e = na2d_check(c, K)) return e;                // the limits of the bf16 kernels (na2d.h)
+    p.B = B; p.H = H; p.W = W; p.nH = nH; p.K = K; p.d = dilation; p.scale = scale;
+    return UENC_OK;
+}
+
+extern "C" int uenc_na2d_f32_fwd(const float* qkv, const float* rpb, float* out, float* lse, int B, int H, int W, int nH, int K, int dilation,
+                                 float scale, hipStream_t stream) {
+    UENC_CHECK_ARG(qkv != nullptr && out != nullptr);
+    UENC_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0);
+    XNa p{qkv, rpb, out, lse, nullptr, nullptr, nullptr};
+    if (int e = xna_fill(p, B, H, W, nH, K, dilation, scale)) return e;
+    hipLaunchKernelGGL(xna_fwd_kernel, dim3((W + 63) / 64, H, B * nH), dim3(256), 0, stream, p);
+    UENC_LAUNCH_RET();
+}
+
+// dqkv (B, H, W, 3, nH, 32) is written completely; drpb (nH, 2K-1, 2K-1) is ACCUMULATED into (atomics; may be null).
+extern "C" int uenc_na2d_f32_bwd(const float* qkv, const float* rpb, const float* out, const float* dout, const float* lse, float* dqkv,
+                                 float* drpb, int B, int H, int W, int nH, int K, int dilation, float scale, hipStream_t stream) {
+    UENC_CHECK_ARG(qkv != nullptr && out != nullptr && dout != nullptr && lse != nullptr && dqkv != nullptr);
+    UENC_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) == 0);
+    XNa p{qkv, rpb, const_cast<float*>(out), const_cast<float*>(lse), dout, dqkv, drpb};      // (out is read: delta = dO . O)
+    if (int e = xna_fill(p, B, H, W, nH, K, dilation, scale)) return e;
+    const hipError_t z = hipMemsetAsync(dqkv, 0, (size_t)B * H * W * 3 * nH * XHD * sizeof(float), stream);
+    if (z != hipSuccess) return (int)z;
+    hipLaunchKernelGGL(xna_bwd_kernel, dim3((W + 63) / 64, H, B * nH), dim3(64), 0, stream, p);
     UENC_LAUNCH_RET();
 }

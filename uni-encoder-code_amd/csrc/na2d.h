@@ -22,6 +22,14 @@ __device__ __forceinline__ AxisWin axis_win(int t, int len, int d, int K) {
     return a;
 }
 
+static int na2d_check(const Na2d& p, int K) {
+    UENC_CHECK_ARG(p.B > 0 && p.H > 0 && p.W > 0 && p.nH > 0 && p.d >= 1);
+    UENC_CHECK_ARG(K >= 3 && K <= 13 && (K & 1));
+    UENC_CHECK_ARG(p.H >= K * p.d && p.W >= K * p.d);      // the caller zero-pads smaller inputs first, like NATTEN
+    UENC_CHECK_ARG((long)p.B * p.nH <= 65535 && p.H <= 65535);
+    return UENC_OK;
+}
+
 // na2d_mfma.hip
 int na2d_mfma_fwd(const Na2d& p, int K, hipStream_t stream);
 int na2d_mfma_bwd(Na2d& p, int K, hipStream_t stream);

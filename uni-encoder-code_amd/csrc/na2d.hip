@@ -490,14 +490,6 @@ __global__ __launch_bounds__(512) void na2d_bwd_kv_tiled_kernel(Na2d p) {
     *(bf16x8*)(p.dqkv + pix * 3 * C + 2 * C + h * 32 + c8) = ov;
 }
 
-static int na2d_check(const Na2d& p, int K) {
-    UENC_CHECK_ARG(p.B > 0 && p.H > 0 && p.W > 0 && p.nH > 0 && p.d >= 1);
-    UENC_CHECK_ARG(K >= 3 && K <= 13 && (K & 1));
-    UENC_CHECK_ARG(p.H >= K * p.d && p.W >= K * p.d);      // the caller zero-pads smaller inputs first, like NATTEN
-    UENC_CHECK_ARG((long)p.B * p.nH <= 65535 && p.H <= 65535);
-    return UENC_OK;
-}
-
 #define NA2D_DISPATCH(KERNEL)                                                                                   \
     switch (K) {                                                                                                \
         case 3: hipLaunchKernelGGL(KERNEL<3>, grid, dim3(256), 0, stream, p); break;                            \

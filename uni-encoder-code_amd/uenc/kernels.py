@@ -338,6 +338,14 @@ def im2col3x3_s2(x16: torch.Tensor) -> torch.Tensor:
 
 def col2im3x3_s2(dcol: torch.Tensor, B: int, H: int, W: int, C: int) -> torch.Tensor:
     """adjoint of im2col3x3_s2: (rows, 9C) bf16 -> (B, H, W, C) fp32."""
+    if EXACT and dcol.dtype == torch.float32:   # adjoint of the strided gather as nine shifted fp32 adds (verification mode only)
+        Ho, Wo = (H + 1) // 2, (W + 1) // 2
+        d = dcol.view(B, Ho, Wo, 9, C)
+        dxp = dcol.new_zeros((B, 2 * Ho + 2, 2 * Wo + 2, C))
+        for t in range(9):
+            ky, kx = divmod(t, 3)
+            dxp[:, ky:ky + 2 * Ho:2, kx:kx + 2 * Wo:2] += d[:, :, :, t]
+        return dxp[:, 1:1 + H, 1:1 + W].contiguous()
     assert dcol.dtype == torch.bfloat16 and dcol.is_contiguous() and dcol.shape[1] == 9 * C
     dx = torch.empty((B, H, W, C), dtype=torch.float32, device=dcol.device)
     check(lib.uenc_col2im3x3_s2(dcol.data_ptr(), dx.data_ptr(), B, H, W, C, stream_ptr()), "col2im3x3_s2")
@@ -345,14 +353,20 @@ def col2im3x3_s2(dcol: torch.Tensor, B: int, H: int, W: int, C: int) -> torch.Te
 
 
 def na2d_fwd(qkv: torch.Tensor, rpb: Optional[torch.Tensor], nH: int, ks: int, dilation: int, scale: float, need_lse: bool = True):
-    """Neighbourhood attention on qkv (B, H, W, 3C) bf16 (C = nH * 32) -> out (B, H, W, C) bf16, lse (B, nH, H, W) fp32."""
+    """Neighbourhood attention on qkv (B, H, W, 3C) bf16 (C = nH * 32) -> out (B, H, W, C) bf16, lse (B, nH, H, W) fp32.
+    Exact mode: qkv and out fp32 (uenc_na2d_f32_fwd)."""
     B, H, W, C3 = qkv.shape
     C = C3 // 3
-    if EXACT:
-        raise NotImplementedError("the fp32 exact mode covers the Swin path; neighbourhood attention has no fp32 kernel")
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and C == nH * 32, "na2d: head_dim must be 32"
     if rpb is not None:
         assert rpb.dtype == torch.float32 and rpb.is_contiguous() and tuple(rpb.shape) == (nH, 2 * ks - 1, 2 * ks - 1)
+    if EXACT:
+        assert qkv.dtype == torch.float32 and qkv.is_contiguous() and C == nH * 32, "na2d: head_dim must be 32"
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((B, nH, H, W), dtype=torch.float32, device=qkv.device) if need_lse else None
+        check(lib.uenc_na2d_f32_fwd(qkv.data_ptr(), ptr(rpb), out.data_ptr(), ptr(lse), B, H, W, nH, ks, dilation, float(scale), stream_ptr()),
+              "na2d_f32_fwd")
+        return out, lse
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and C == nH * 32, "na2d: head_dim must be 32"
     out = torch.empty((B, H, W, C), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, nH, H, W), dtype=torch.float32, device=qkv.device) if need_lse else None
     check(lib.uenc_na2d_fwd(qkv.data_ptr(), ptr(rpb), out.data_ptr(), ptr(lse), B, H, W, nH, ks, dilation, float(scale), stream_ptr()),
@@ -361,8 +375,16 @@ def na2d_fwd(qkv: torch.Tensor, rpb: Optional[torch.Tensor], nH: int, ks: int, d
 
 
 def na2d_bwd(qkv, rpb, out, dout, lse, nH: int, ks: int, dilation: int, scale: float, drpb: Optional[torch.Tensor]):
-    """-> dqkv (B, H, W, 3C) bf16; drpb (nH, 2ks-1, 2ks-1) fp32 is accumulated in place when given."""
+    """-> dqkv (B, H, W, 3C) bf16; drpb (nH, 2ks-1, 2ks-1) fp32 is accumulated in place when given.  Exact mode: qkv, out, dout
+    and dqkv fp32 (uenc_na2d_f32_bwd)."""
     B, H, W, C3 = qkv.shape
+    if EXACT:
+        assert qkv.dtype == torch.float32 and qkv.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
+        assert dout.dtype == torch.float32 and dout.is_contiguous() and dout.shape == out.shape
+        dqkv = torch.empty_like(qkv)
+        check(lib.uenc_na2d_f32_bwd(qkv.data_ptr(), ptr(rpb), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), ptr(drpb),
+                                    B, H, W, nH, ks, dilation, float(scale), stream_ptr()), "na2d_f32_bwd")
+        return dqkv
     assert dout.dtype == torch.bfloat16 and dout.is_contiguous() and out.is_contiguous() and dout.shape == out.shape
     dqkv = torch.empty_like(qkv)
     ws = _scratch("na2d_delta", B * nH * H * W * 4, qkv.device)

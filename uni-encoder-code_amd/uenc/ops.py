@@ -1407,7 +1407,8 @@ def conv3x3_group_norm(x_nhwc, weight, gn, *, relu=False, out_dtype=F32):
 # --------------------------------------------------------------------------------------------
 class NA2DFn(torch.autograd.Function):
     """natten2dqkrpb + softmax + natten2dav of natten.NeighborhoodAttention2D (reference call site backbone/dinat.py:77-79) on the
-    qkv Linear's output (B, H, W, 3C) bf16 -> (B, H, W, C) bf16.  H, W >= ks * dilation (the module pads first, like NATTEN)."""
+    qkv Linear's output (B, H, W, 3C) bf16 -> (B, H, W, C) bf16 (fp32 in exact mode).  H, W >= ks * dilation (the module pads first,
+    like NATTEN)."""
 
     @staticmethod
     def forward(ctx, qkv, rpb, nH, ks, dilation, scale):
@@ -1422,7 +1423,7 @@ class NA2DFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, rpb, out, lse = ctx.saved_tensors
         nH, ks, dilation, scale = ctx.cfg
-        dout = dout if dout.dtype == BF16 else dout.to(BF16)
+        dout = dout if dout.dtype == K.adt() else dout.to(K.adt())
         train = rpb is not None and rpb.requires_grad
         dqkv = K.na2d_bwd(qkv, None if rpb is None else rpb.detach().float().contiguous(), out, dout.contiguous(), lse, nH, ks, dilation, scale,
                           grad_buf(rpb) if train else None)
@@ -1454,7 +1455,7 @@ class NATLayerFn(torch.autograd.Function):
         attn, lse = K.na2d_fwd(qkv.view(B, H, W, 3 * C), rp, nH, ks, dilation, scale)
         x1 = _branch_gemm(attn.view(M, C), CACHE.mat(wproj), bproj.detach(), x2, C, s1)
         xn2, _, st2 = K.layernorm_fwd(x1, g2.detach(), b2.detach(), out_dtype=BF16)
-        pre = torch.empty((M, w1.shape[0]), dtype=BF16, device=x.device)
+        pre = torch.empty((M, w1.shape[0]), dtype=K.adt(), device=x.device)
         h = K.gemm_nt(xn2, CACHE.mat(w1), bias=bb1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
         x2o = _branch_gemm(h, CACHE.mat(w2), bb2.detach(), x1, C, s2)
         ctx.dp = (s1, s2)
@@ -1543,7 +1544,7 @@ class ConvS2Fn(torch.autograd.Function):
         Co = weight.shape[0]
         Ho, Wo = (H + 1) // 2, (W + 1) // 2
         Kp = -(-9 * C // 8) * 8
-        x16 = x if x.dtype == BF16 else x.to(BF16)
+        x16 = x if x.dtype == K.adt() else x.to(K.adt())          # (exact mode: the fp32 image / tokens as they are)
         # patch matrix by the HIP gather when the channel count allows 16-byte pieces, else by strided slices (the 3-channel image)
         col = K.im2col3x3_s2(x16.contiguous()) if C % 8 == 0 else ConvS2Fn._patches(x16, Ho, Wo, Kp)
         Np = -(-Co // 8) * 8
