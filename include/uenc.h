@@ -386,6 +386,34 @@ int uenc_na2d_f32_fwd(const float* qkv, const float* rpb, float* out, float* lse
 int uenc_na2d_f32_bwd(const float* qkv, const float* rpb, const float* out, const float* dout, const float* lse, float* dqkv, float* drpb,
                       int B, int H, int W, int nH, int K, int dilation, float scale, uenc_stream_t stream);
 
+/* ---- device-side per-step randomness (capturable training step, uenc/graphs.py) ---------------------------------------------- */
+/* state = {64-bit base seed, 64-bit step counter} in device memory.  advance != 0: step += 1 first (by the kernel: a replayed graph
+ * needs no host input).  Then, with key = mix(base, step) (the attn_keep hash):
+ *   scales[s * n_samples + b] = keep ? 1 / keep_prob[s] : 0,  keep = hash(key, 2^41 | (s n_samples + b)) >= (1 - keep_prob[s]) 2^32
+ *   seeds[j] = hash(key, 2^40 | j)
+ * for the n_branch DropPath branch slots and n_seed dropout seed slots.  Pure functions of (base, step, slot, sample). */
+int uenc_step_rng_advance(unsigned long long* state, const float* keep_prob, int n_branch, int n_samples, float* scales, int n_seed,
+                          unsigned* seeds, int advance, uenc_stream_t stream);
+/* Inverted dropout of n elements (dtype UENC_F32 / UENC_BF16, any n, in place allowed) with the seed read from seeds[slot] on the device:
+ * the keep-mask of uenc_dropout_bf16, bit-identical to it for bf16 and the same seed. */
+int uenc_dropout_sp(const void* in, void* out, long n, int dtype, const unsigned* seeds, int slot, float p, uenc_stream_t stream);
+/* out[r][:C] = bf16(in[r][:C] * sample_scale[r / rows_per_sample]) for r < M (bf16 rows, C % 8 == 0, 16-byte aligned rows): the
+ * DropPath-scaled gradient a branch's weight-gradient GEMM reads when the multipliers live on the device. */
+int uenc_scale_rows_bf16(const void* in, long ld_in, void* out, long ld_out, long M, int C, const float* sample_scale, long rows_per_sample,
+                         uenc_stream_t stream);
+/* hipMemcpyAsync of `bytes` from pinned host memory to the device on `stream` (the descriptor uploads of a captured step). */
+int uenc_upload(void* dst, const void* src, long bytes, uenc_stream_t stream);
+/* uenc_mha_fwd / uenc_mha_bwd with the dropout seed read from seeds[slot] on the device (bit-identical for the same seed). */
+int uenc_mha_fwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                    long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse,
+                    float* workspace, int B, int H, int Lq, int S, float scale, float dropout_p, const unsigned* seeds, int slot,
+                    uenc_stream_t stream);
+int uenc_mha_bwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                    long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs,
+                    const float* lse, const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk,
+                    long dk_bs, long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale,
+                    float dropout_p, const unsigned* seeds, int slot, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);
@@ -394,6 +422,8 @@ int uenc_prof_collect_bytes(int kind, double* bytes_total);
 /* algorithmic bytes of the NEXT recorded launch whose entry point cannot derive them (the grouped wgrad launches read their
  * problem sizes from a device table the caller built). */
 int uenc_prof_next_bytes(double bytes);
+/* 1 while the launch timers are on (a captured graph would replay their event records: uenc/graphs.py refuses to capture then). */
+int uenc_prof_active(void);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ struct MhaP {
     int B, H, Lq, S, nsplit, keys_per_split;
     float scale;
     unsigned drop_thresh, seed;                     // attention-probability dropout (0 = off): attn_keep() of common.h
+    const unsigned* seed_ptr;                       // non-NULL: the seed is read from this device word instead (the *_sp entries)
     float inv_keep;
 };
 
@@ -92,6 +93,7 @@ __global__ __launch_bounds__(256, 2) void mha_q_kernel(MhaP p) {
 
     int split, bh;
     if (!mha_decode_block(p, split, bh)) return;
+    const unsigned seed = DROP ? (p.seed_ptr != nullptr ? *p.seed_ptr : p.seed) : 0u;
     const int q0 = blockIdx.z * MQ;
     const int b = bh / p.H, h = bh - b * p.H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fg = lane >> 4;
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void mha_q_kernel(MhaP p) {
                         sum += e;                                    // the softmax normaliser is taken BEFORE dropout
                         v[kt][r] = e;
                         if (DROP)
-                            v[kt][r] = attn_keep(p.seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qidx[i]) * p.S + (kbase + kt * 16 + 4 * fg + r))
+                            v[kt][r] = attn_keep(seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qidx[i]) * p.S + (kbase + kt * 16 + 4 * fg + r))
                                            ? e * p.inv_keep : 0.f;
                     }
                 sum = xor16_sum(sum);
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void mha_q_kernel(MhaP p) {
                         const float pr = fast_exp2(__builtin_fmaf(v[kt][r], sc, -lse_q[i]));
                         float dpv = dp[r];
                         if (DROP)
-                            dpv = attn_keep(p.seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qidx[i]) * p.S + (kbase + kt * 16 + 4 * fg + r))
+                            dpv = attn_keep(seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qidx[i]) * p.S + (kbase + kt * 16 + 4 * fg + r))
                                       ? dpv * p.inv_keep : 0.f;
                         v[kt][r] = pr * (dpv - dl_q[i]);
                     }
@@ -342,6 +344,7 @@ template <bool DROP>
 __global__ __launch_bounds__(256, 2) void mha_dkdv_kernel(MhaP p) {
     constexpr int NQB = MQT / 2;     // 32-query blocks
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const unsigned seed = DROP ? (p.seed_ptr != nullptr ? *p.seed_ptr : p.seed) : 0u;
     const int nslices = (p.Lq + MQ - 1) / MQ;
     unsigned char* Qs = smem;                                   // nslices x MQ rows
     unsigned char* dOs = Qs + (long)nslices * MQ * 64;
@@ -459,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void mha_dkdv_kernel(MhaP p) {
                     float keepw = 1.0f;
                     const bool ok = DROP && (key < k_end) && (qi < p.Lq) && pr != 0.f;
                     if (DROP && ok)
-                        keepw = attn_keep(p.seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qi) * p.S + key) ? p.inv_keep : 0.f;
+                        keepw = attn_keep(seed, p.drop_thresh, ((unsigned long long)bh * p.Lq + qi) * p.S + key) ? p.inv_keep : 0.f;
                     pt[h2][r] = pr * keepw;
                     dst[h2][r] = pr * (dp[r] * keepw - dv4[r]);
                 }
@@ -523,7 +526,7 @@ static int mha_fill(MhaP& p, const void* q, long q_bs, long q_rs, const void* k,
                     long v_rs, const unsigned char* mask, long mask_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
                     unsigned seed) {
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return UENC_EINVAL;
-    p.drop_thresh = attn_drop_thresh(dropout_p); p.seed = seed; p.inv_keep = 1.0f / (1.0f - dropout_p);
+    p.drop_thresh = attn_drop_thresh(dropout_p); p.seed = seed; p.seed_ptr = nullptr; p.inv_keep = 1.0f / (1.0f - dropout_p);
     if (!(q && k && v && B > 0 && H > 0 && Lq > 0 && S > 0)) return UENC_EINVAL;
     if ((q_rs | k_rs | v_rs | q_bs | k_bs | v_bs) & 7) return UENC_EINVAL;                   // 16-byte rows
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return UENC_EINVAL;
@@ -539,12 +542,13 @@ static int mha_fill(MhaP& p, const void* q, long q_bs, long q_rs, const void* k,
 // dropout_p / seed: dropout on the attention probabilities (training mode of nn.MultiheadAttention(dropout=p)); 0 = off.
 // out (B, Lq, H*32-wide rows) bf16; lse (B, H, Lq) fp32 (log2 domain, needed by the backward; may be NULL);
 // workspace: uenc_mha_fwd_workspace_floats() floats (may be NULL when that is 0).
-extern "C" int uenc_mha_fwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
-                            long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse, float* workspace,
-                            int B, int H, int Lq, int S, float scale, float dropout_p, unsigned seed, hipStream_t stream) {
+static int mha_fwd_impl(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                        long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse, float* workspace,
+                        int B, int H, int Lq, int S, float scale, float dropout_p, unsigned seed, const unsigned* seed_ptr, hipStream_t stream) {
     MhaP p;
     int rc = mha_fill(p, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, B, H, Lq, S, scale, dropout_p, seed);
     if (rc != UENC_OK) return rc;
+    p.seed_ptr = seed_ptr;
     UENC_CHECK_ARG(out && (o_rs % 4 == 0) && (o_bs % 4 == 0));
     p.out = (bf16*)out; p.o_bs = o_bs; p.o_rs = o_rs; p.lse = lse;
     const int slices = (Lq + MQ - 1) / MQ;
@@ -563,14 +567,15 @@ extern "C" int uenc_mha_fwd(const void* q, long q_bs, long q_rs, const void* k, 
 }
 
 // dq (B, Lq, *) fp32 accumulated (caller zeroes); dk, dv (B, S, *) bf16 overwritten for every key.
-extern "C" int uenc_mha_bwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
-                            long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs, const float* lse,
-                            const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs,
-                            long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
-                            unsigned seed, hipStream_t stream) {
+static int mha_bwd_impl(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                        long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs, const float* lse,
+                        const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs,
+                        long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
+                        unsigned seed, const unsigned* seed_ptr, hipStream_t stream) {
     MhaP p;
     int rc = mha_fill(p, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, B, H, Lq, S, scale, dropout_p, seed);
     if (rc != UENC_OK) return rc;
+    p.seed_ptr = seed_ptr;
     UENC_CHECK_ARG(out && lse && dout && dq && dk && dv);
     UENC_CHECK_ARG(((o_rs | do_rs | o_bs | do_bs) & 7) == 0 && ((dk_rs | dv_rs | dk_bs | dv_bs) & 3) == 0);
     p.out = (bf16*)out; p.o_bs = o_bs; p.o_rs = o_rs; p.lse = (float*)lse;
@@ -591,4 +596,40 @@ extern "C" int uenc_mha_bwd(const void* q, long q_bs, long q_rs, const void* k, 
     if (drop) hipLaunchKernelGGL(mha_dkdv_kernel<true>, dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16)), dim3(256), shm, stream, p);
     else hipLaunchKernelGGL(mha_dkdv_kernel<false>, dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16)), dim3(256), shm, stream, p);
     UENC_LAUNCH_RET();
+}
+
+extern "C" int uenc_mha_fwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                            long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse, float* workspace,
+                            int B, int H, int Lq, int S, float scale, float dropout_p, unsigned seed, hipStream_t stream) {
+    return mha_fwd_impl(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, out, o_bs, o_rs, lse, workspace, B, H, Lq, S, scale,
+                        dropout_p, seed, nullptr, stream);
+}
+
+extern "C" int uenc_mha_bwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                            long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs, const float* lse,
+                            const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs,
+                            long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
+                            unsigned seed, hipStream_t stream) {
+    return mha_bwd_impl(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, out, o_bs, o_rs, lse, dout, do_bs, do_rs, dq, dq_bs, dq_rs,
+                        dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, B, H, Lq, S, scale, dropout_p, seed, nullptr, stream);
+}
+
+// Seed-by-pointer twins (HIP-graph capture): the dropout seed is seeds[slot], a device word written by uenc_step_rng_advance, read by the
+// kernels themselves -- a replay picks up the step's fresh seed without any host argument.  Same arithmetic as the by-value entries.
+extern "C" int uenc_mha_fwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                               long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse, float* workspace,
+                               int B, int H, int Lq, int S, float scale, float dropout_p, const unsigned* seeds, int slot, hipStream_t stream) {
+    UENC_CHECK_ARG(seeds != nullptr && slot >= 0);
+    return mha_fwd_impl(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, out, o_bs, o_rs, lse, workspace, B, H, Lq, S, scale,
+                        dropout_p, 0u, seeds + slot, stream);
+}
+
+extern "C" int uenc_mha_bwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                               long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs, const float* lse,
+                               const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs,
+                               long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
+                               const unsigned* seeds, int slot, hipStream_t stream) {
+    UENC_CHECK_ARG(seeds != nullptr && slot >= 0);
+    return mha_bwd_impl(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, mask, mask_rs, out, o_bs, o_rs, lse, dout, do_bs, do_rs, dq, dq_bs, dq_rs,
+                        dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, B, H, Lq, S, scale, dropout_p, 0u, seeds + slot, stream);
 }

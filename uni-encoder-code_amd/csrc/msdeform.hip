@@ -910,6 +910,25 @@ __device__ __forceinline__ Bf3 split3(float v) {
     return o;
 }
 
+// Zeroes the bin counters of the binned backward.  Eagerly one hipMemsetAsync; while the stream is being captured into a HIP graph a
+// kernel does it, so that the captured step holds kernel nodes only (a replay whose counters were not reset would let the reduce kernel
+// read record slots no pass wrote).
+__global__ __launch_bounds__(256) void msda_zero_counts_kernel(int* __restrict__ count, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) count[i] = 0;
+}
+
+static hipError_t msda_zero_counts(int* count, long bytes, hipStream_t stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive) {
+        const long n = bytes / 4;
+        long blocks = (n + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(msda_zero_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, count, n);
+        return hipGetLastError();
+    }
+    return hipMemsetAsync(count, 0, (size_t)bytes, stream);
+}
+
 template <bool GO_F32>
 __global__ __launch_bounds__(256) void msda_bin_reduce_kernel(MsdaP p, MsdaBins bn) {
     constexpr int D = 32, NT = GO_F32 ? 3 : 1;
@@ -1156,7 +1175,7 @@ extern "C" int uenc_msdeform_attn_bwd(const void* value, int v_dtype, const int6
         bn.count = (int*)workspace;
         bn.rec_w = (float4*)((char*)workspace + cnt_bytes);                     // 16-byte records first (alignment)
         bn.rec_hd = (int2*)((char*)workspace + cnt_bytes + (long)B * M * bn.rtot * 16);
-        hipError_t e = hipMemsetAsync(bn.count, 0, (size_t)cnt_bytes, stream);
+        hipError_t e = msda_zero_counts(bn.count, cnt_bytes, stream);
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, dim3((unsigned)(nchunk * B * M)), dim3(256), 0, stream, p, bn);
         if (p.go_f32) hipLaunchKernelGGL(msda_bin_reduce_kernel<true>, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, stream, p, bn);
@@ -1248,7 +1267,7 @@ extern "C" int uenc_msdeform_attn_fused_bwd(const void* value, int v_dtype, cons
     bn.count = (int*)workspace;
     bn.rec_w = (float4*)((char*)workspace + cnt_bytes);
     bn.rec_hd = (int2*)((char*)workspace + cnt_bytes + (long)B * M * bn.rtot * 16);
-    hipError_t e = hipMemsetAsync(bn.count, 0, (size_t)cnt_bytes, stream);
+    hipError_t e = msda_zero_counts(bn.count, cnt_bytes, stream);
     if (e != hipSuccess) return (int)e;
     // encoder geometry (queries = the maps' pixels, P == 4, 16-byte aligned rows): d(offaw) from the LDS-tiled kernel, the binned kernel only
     // appends its records.  UENC_MSDA_TILED_BWD=0: the one-kernel form (A/B).

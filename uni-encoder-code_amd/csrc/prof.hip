@@ -28,6 +28,8 @@ hipEvent_t get_event() {
 
 bool uenc_prof_on() { return g_on; }
 
+extern "C" int uenc_prof_active(void) { return g_on ? 1 : 0; }
+
 void uenc_prof_begin(int kind, double flops, hipStream_t stream, double bytes) {
     if (bytes == 0.0) bytes = g_next_bytes;
     g_next_bytes = 0.0;

@@ -43,6 +43,8 @@ class MHACoreFn(torch.autograd.Function):
         m8, mrs = _mask_bytes(mask)
         lse = torch.empty((B, nheads, Lq), dtype=torch.float32, device=q.device)
         if K.EXACT:                                      # fp32 operands, csrc/exact.hip
+            if isinstance(seed, K.SeedSlot):
+                raise RuntimeError("device-side dropout seeds (ops.device_rng) are not available in the fp32 exact mode")
             out = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
             check(lib.uenc_mha_f32_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
                                        v.data_ptr(), v.stride(0), v.stride(1), m8.data_ptr() if m8 is not None else 0, mrs,
@@ -54,13 +56,16 @@ class MHACoreFn(torch.autograd.Function):
         out = torch.empty((B, Lq, E), dtype=torch.bfloat16, device=q.device)
         nws = lib.uenc_mha_fwd_workspace_floats(B, nheads, Lq, S)
         ws = torch.empty((nws,), dtype=torch.float32, device=q.device) if nws else None
-        check(lib.uenc_mha_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
-                               v.data_ptr(), v.stride(0), v.stride(1), m8.data_ptr() if m8 is not None else 0, mrs,
-                               out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(),
-                               ws.data_ptr() if ws is not None else 0, B, nheads, Lq, S, scale, float(dropout_p), int(seed), stream_ptr()),
-              "mha_fwd")
+        args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                v.data_ptr(), v.stride(0), v.stride(1), m8.data_ptr() if m8 is not None else 0, mrs,
+                out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(),
+                ws.data_ptr() if ws is not None else 0, B, nheads, Lq, S, scale, float(dropout_p))
+        if isinstance(seed, K.SeedSlot):                 # seed read on the device (capturable step, ops.device_rng)
+            check(lib.uenc_mha_fwd_sp(*args, seed.seeds.data_ptr(), seed.slot, stream_ptr()), "mha_fwd_sp")
+        else:
+            check(lib.uenc_mha_fwd(*args, int(seed), stream_ptr()), "mha_fwd")
         ctx.save_for_backward(q, k, v, out, lse, m8 if m8 is not None else torch.empty(0, device=q.device))
-        ctx.meta = (nheads, S, scale, mrs, m8 is not None, float(dropout_p), int(seed))
+        ctx.meta = (nheads, S, scale, mrs, m8 is not None, float(dropout_p), seed if isinstance(seed, K.SeedSlot) else int(seed))
         return out
 
     @staticmethod
@@ -85,12 +90,17 @@ class MHACoreFn(torch.autograd.Function):
         dq = torch.zeros((B, Lq, E), dtype=torch.float32, device=q.device)
         dk = torch.empty((B, S, E), dtype=torch.bfloat16, device=q.device)
         dv = torch.empty((B, S, E), dtype=torch.bfloat16, device=q.device)
-        check(lib.uenc_mha_bwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
-                               v.data_ptr(), v.stride(0), v.stride(1), m8.data_ptr() if has_mask else 0, mrs,
-                               out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(),
-                               dout.data_ptr(), dout.stride(0), dout.stride(1),
-                               dq.data_ptr(), dq.stride(0), dq.stride(1), dk.data_ptr(), dk.stride(0), dk.stride(1),
-                               dv.data_ptr(), dv.stride(0), dv.stride(1), B, nheads, Lq, S, scale, dropout_p, seed, stream_ptr()), "mha_bwd")
+        args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                v.data_ptr(), v.stride(0), v.stride(1), m8.data_ptr() if has_mask else 0, mrs,
+                out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(),
+                dout.data_ptr(), dout.stride(0), dout.stride(1),
+                dq.data_ptr(), dq.stride(0), dq.stride(1), dk.data_ptr(), dk.stride(0), dk.stride(1),
+                dv.data_ptr(), dv.stride(0), dv.stride(1), B, nheads, Lq, S, scale, dropout_p)
+        if isinstance(seed, K.SeedSlot):
+            seed.check()
+            check(lib.uenc_mha_bwd_sp(*args, seed.seeds.data_ptr(), seed.slot, stream_ptr()), "mha_bwd_sp")
+        else:
+            check(lib.uenc_mha_bwd(*args, seed, stream_ptr()), "mha_bwd")
         return dq.to(torch.bfloat16), dk, dv, None, None, None, None
 
 

@@ -81,6 +81,15 @@ _SIGNATURES = {
     "uenc_na2d_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "uenc_na2d_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "uenc_window_attn_bwd_ws_floats": [c_i, c_i, c_i, c_i, c_i],
+    # device-side per-step randomness (csrc/step_rng.hip) and the seed-by-pointer attention twins
+    "uenc_step_rng_advance": [c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p],
+    "uenc_dropout_sp": [c_p, c_p, c_l, c_i, c_p, c_i, c_f, c_p],
+    "uenc_upload": [c_p, c_p, c_l, c_p],
+    "uenc_prof_active": [],
+    "uenc_scale_rows_bf16": [c_p, c_l, c_p, c_l, c_l, c_i, c_p, c_l, c_p],
+    "uenc_mha_fwd_sp": [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_i, c_p],
+    "uenc_mha_bwd_sp": [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_l, c_l, c_p, c_l, c_l,
+                        c_p, c_l, c_l, c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_i, c_p],
     # fp32 exact mode (csrc/exact.hip)
     "uenc_gemm_nt_f32": [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_f, c_i, c_p],
     "uenc_gemm_tn_f32": [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_i, c_p],

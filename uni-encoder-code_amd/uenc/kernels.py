@@ -38,12 +38,65 @@ def _mat(t: torch.Tensor, name: str):
     return t
 
 
-def dropout_bf16(x16: torch.Tensor, seed: int, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Inverted dropout of a contiguous bf16 tensor with the index-hash keep mask (uenc_dropout_bf16); out=x16 for in place."""
+# While a training step is being captured into a HIP graph (uenc/graphs.py): [pinned uint8 host buffer, next free offset].  Descriptor
+# tables are then staged in this buffer, which the captured step owns for the graph's lifetime, and copied by uenc_upload: every replay
+# re-reads them from there.  (A temporary pinned tensor would be recycled by torch's host allocator once freed.)
+CAPTURE_ARENA = None
+
+
+def upload_table(arr, device, pinned: bool = True) -> torch.Tensor:
+    """Device copy of a numpy descriptor table (raw bytes).  Eager: a pinned (or, pinned=False, pageable) temporary and torch's copy, as the
+    launch sites always did; during a capture: staged in the capture's host arena."""
+    import numpy as np
+    raw = arr.view(np.uint8).reshape(-1)
+    if CAPTURE_ARENA is None:
+        if not pinned:
+            return torch.from_numpy(raw.copy()).to(device)
+        return torch.from_numpy(raw).pin_memory().to(device, non_blocking=True)
+    host, off = CAPTURE_ARENA[0], CAPTURE_ARENA[1]
+    n = int(raw.size)
+    end = off + -(-n // 256) * 256
+    if end > host.numel():
+        raise RuntimeError(f"captured step: descriptor tables exceed the capture's {host.numel()} byte host arena")
+    host[off:off + n].numpy()[:] = raw
+    CAPTURE_ARENA[1] = end
+    tab = torch.empty(n, dtype=torch.uint8, device=device)
+    check(lib.uenc_upload(tab.data_ptr(), host.data_ptr() + off, n, stream_ptr()), "upload")
+    return tab
+
+
+class SeedSlot:
+    """A dropout seed that lives on the device: word `slot` of the seed table `seeds` (uint32 as int32), written once per step by
+    uenc_step_rng_advance.  Kernels given a SeedSlot read the seed themselves (the *_sp entry points), so a replayed graph draws the
+    step's fresh mask."""
+    __slots__ = ("seeds", "slot", "owner", "gen")
+
+    def __init__(self, seeds: torch.Tensor, slot: int, owner=None):
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and 0 <= slot < seeds.numel()
+        self.seeds, self.slot, self.owner = seeds, int(slot), owner
+        self.gen = owner.generation if owner is not None else 0
+
+    def check(self):
+        """owner: the ops.DeviceRNG that wrote the table; refuses a use after it moved on to another step (begin_step between a forward
+        and its backward)."""
+        if self.owner is not None and self.owner.generation != self.gen:
+            raise RuntimeError("device RNG: ops.begin_step() ran between this dropout's forward and its backward -- the seed table now "
+                               "holds the next step's seeds")
+
+    def value(self) -> int:
+        """The seed as a python int (a device sync: tests only)."""
+        return int(self.seeds[self.slot].item()) & 0xFFFFFFFF
+
+
+def dropout_bf16(x16: torch.Tensor, seed, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverted dropout of a contiguous bf16 tensor with the index-hash keep mask (uenc_dropout_bf16); out=x16 for in place.
+    seed: an int, or a SeedSlot (uenc_dropout_sp: the same mask, seed read on the device)."""
     assert x16.dtype == torch.bfloat16 and x16.is_contiguous() and x16.is_cuda and x16.numel() % 8 == 0
     if out is None:
         out = torch.empty_like(x16)
     assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == x16.numel()
+    if isinstance(seed, SeedSlot):
+        return dropout_sp(x16, seed, p, out=out)
     check(lib.uenc_dropout_bf16(x16.data_ptr(), out.data_ptr(), x16.numel(), int(seed) & 0xFFFFFFFF, float(p), stream_ptr()), "dropout_bf16")
     return out
 
@@ -55,6 +108,74 @@ def dropout_keep_reference(shape, p: float, seed: int) -> torch.Tensor:
     for d in shape:
         n *= int(d)
     return keep_mask_reference(1, 1, 1, n, p, int(seed) & 0xFFFFFFFF).view(tuple(shape))
+
+
+def dropout_sp(x: torch.Tensor, seed: SeedSlot, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverted dropout of a contiguous fp32 / bf16 tensor (any size) with the seed read from the device table (uenc_dropout_sp):
+    the keep-mask of `dropout_keep_reference(x.shape, p, seed)`.  out=x for in place."""
+    assert x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16) and isinstance(seed, SeedSlot)
+    seed.check()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == x.dtype and out.is_contiguous() and out.numel() == x.numel()
+    if x.numel():
+        check(lib.uenc_dropout_sp(x.data_ptr(), out.data_ptr(), x.numel(), dt(x), seed.seeds.data_ptr(), seed.slot, float(p), stream_ptr()),
+              "dropout_sp")
+    return out
+
+
+def scale_rows_bf16(g16: torch.Tensor, sample_scale: torch.Tensor, rows_per_sample: int) -> torch.Tensor:
+    """bf16 copy of a (M, C) gradient with the rows of sample b multiplied by sample_scale[b] (device fp32)."""
+    g16 = _mat(g16, "g16")
+    assert g16.dtype == torch.bfloat16 and sample_scale.dtype == torch.float32 and sample_scale.is_cuda
+    M, C = g16.shape
+    out = torch.empty((M, C), dtype=torch.bfloat16, device=g16.device)
+    check(lib.uenc_scale_rows_bf16(g16.data_ptr(), g16.stride(0), out.data_ptr(), C, M, C, sample_scale.data_ptr(), int(rows_per_sample),
+                                   stream_ptr()), "scale_rows_bf16")
+    return out
+
+
+def step_rng_advance(state: torch.Tensor, keep_prob: torch.Tensor, n_branch: int, n_samples: int, scales: torch.Tensor, n_seed: int,
+                     seeds: torch.Tensor, advance: bool = True):
+    """uenc_step_rng_advance: state (2,) int64 {base seed, step} on the device; keep_prob (>= n_branch,) fp32; scales (>= n_branch * n_samples,)
+    fp32; seeds (>= n_seed,) int32 (uint32 bits)."""
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_cuda
+    assert keep_prob.dtype == torch.float32 and scales.dtype == torch.float32 and seeds.dtype == torch.int32
+    assert keep_prob.numel() >= n_branch and scales.numel() >= n_branch * n_samples and seeds.numel() >= n_seed
+    check(lib.uenc_step_rng_advance(state.data_ptr(), keep_prob.data_ptr(), int(n_branch), int(n_samples), scales.data_ptr(), int(n_seed),
+                                    seeds.data_ptr(), int(bool(advance)), stream_ptr()), "step_rng_advance")
+
+
+def _mix32_np(seed, idx):
+    """uenc_mix32 of common.h on numpy uint64 arrays (seed: uint32 values, idx: uint64) -> uint32 values as uint64."""
+    import numpy as np
+    M = np.uint64(0xFFFFFFFF)
+    idx = np.asarray(idx, dtype=np.uint64)
+    x = (((idx & M) ^ (((idx >> np.uint64(32)) * np.uint64(0x9E3779B9)) & M)) + np.asarray(seed, dtype=np.uint64)) & M
+    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & M
+    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & M
+    x ^= x >> np.uint64(16)
+    return x
+
+
+def step_rng_reference(base_seed: int, step: int, keep_prob, n_samples: int, n_seed: int):
+    """The tables uenc_step_rng_advance writes for (base seed, step), restated on the host with numpy integer / fp32 arithmetic.
+    -> (scales (len(keep_prob), n_samples) float32, seeds (n_seed,) uint32).  `step` is the counter value AFTER the advance."""
+    import numpy as np
+    base, step = np.uint64(int(base_seed) & (2 ** 64 - 1)), np.uint64(int(step) & (2 ** 64 - 1))
+    h = _mix32_np(base >> np.uint64(32), step)
+    key = _mix32_np((base & np.uint64(0xFFFFFFFF)) ^ h, step)
+    seeds = _mix32_np(key, np.uint64(1 << 40) | np.arange(n_seed, dtype=np.uint64)).astype(np.uint32)
+    kp = np.asarray(keep_prob, dtype=np.float32)
+    nb = kp.size
+    idx = np.arange(nb * n_samples, dtype=np.uint64)
+    x = _mix32_np(key, np.uint64(1 << 41) | idx).reshape(nb, n_samples)
+    dp = (np.float32(1.0) - kp).astype(np.float32)
+    thresh = np.array([0 if d <= 0 else (0xFFFFFFFF if d >= 1 else int(float(d) * 4294967296.0)) for d in dp], dtype=np.uint64)
+    keep = (kp[:, None] > 0) & (x >= thresh[:, None])
+    inv = (np.float32(1.0) / np.where(kp > 0, kp, np.float32(1.0))).astype(np.float32)
+    scales = np.where(keep, inv[:, None], np.float32(0.0)).astype(np.float32)
+    return scales, seeds
 
 
 def cast_bf16(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -473,7 +594,7 @@ class SmallReductions:
             for i, (part, dg, db, nblk, C) in enumerate(self.ln):
                 desc[i] = (part, dg, db, nblk, C, begin, 0)
                 begin += -(-2 * C // 64)
-            tab = torch.from_numpy(desc.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+            tab = upload_table(desc, dev)
             check(lib.uenc_ln_param_grouped(tab.data_ptr(), len(self.ln), begin, stream_ptr()), "ln_param_grouped")
         if self.dt:
             desc = np.zeros(len(self.dt), dtype=self._DT)
@@ -481,7 +602,7 @@ class SmallReductions:
             for i, (wsd, dtab, G, nH, ws, nt) in enumerate(self.dt):
                 desc[i] = (wsd, dtab, G, nH, ws, nt, begin, 0)
                 begin += nH * nt
-            tab = torch.from_numpy(desc.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+            tab = upload_table(desc, dev)
             check(lib.uenc_window_attn_dtable_grouped(tab.data_ptr(), len(self.dt), begin, stream_ptr()), "window_attn_dtable_grouped")
         self.clear()
 

@@ -140,7 +140,7 @@ class NATLayer(nn.Module):
             x = a(ops.layer_norm(x, self.norm1.weight, self.norm1.bias, out_dtype=torch.bfloat16), residual=x)
             h = ops.layer_norm(x, self.norm2.weight, self.norm2.bias, out_dtype=torch.bfloat16)
             return ops.mlp(h, [self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias], act="gelu", residual=x)
-        s1, s2 = (torch.tensor(v, device=x.device).view(B, 1, 1, 1) for v in dp)
+        s1, s2 = ((v.vec if isinstance(v, ops.DeviceScales) else torch.tensor(v, device=x.device)).view(B, 1, 1, 1) for v in dp)
         x = x + s1 * a(ops.layer_norm(x, self.norm1.weight, self.norm1.bias, out_dtype=torch.bfloat16)).float()
         h = ops.layer_norm(x, self.norm2.weight, self.norm2.bias, out_dtype=torch.bfloat16)
         return x + s2 * ops.mlp(h, [self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias], act="gelu").float()

@@ -67,6 +67,8 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
 
     def _drop(self, t):
         """Inverted dropout with an explicit keep-mask (torch.nn.Dropout semantics: x * mask / keep_prob)."""
+        if ops.device_rng_active():          # capturable step: index-hash mask from a device seed slot (uenc_dropout_sp)
+            return ops.device_dropout(t, self.dropout_p)
         keep = 1.0 - self.dropout_p
         mask = torch.rand(t.shape, device=t.device) < keep
         self._masks.append(mask)
@@ -79,7 +81,8 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         drop = None
         if self.training and self.dropout_p > 0.0 and fusable and not ops.is_exact():
             # three seeds from torch's CPU generator (no device sync); the kernels derive the keep-masks from (seed, element index)
-            self._seeds = tuple(int(v) for v in torch.randint(0, 2 ** 31 - 1, (3,)).tolist())
+            # (device-RNG mode: three seed slots of the step's device table instead)
+            self._seeds = ops.dropout_seeds(3)
             drop = (float(self.dropout_p),) + self._seeds
         elif self.training and self.dropout_p > 0.0:
             # training with dropout: the layer op by op (same kernels), masks applied between them as in the reference (:121-142)

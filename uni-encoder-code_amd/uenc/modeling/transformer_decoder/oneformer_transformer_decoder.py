@@ -66,7 +66,7 @@ class MultiheadAttention(nn.Module):
             k = ops.linear(key, W, b, rows=(E, 2 * E))
         v = ops.linear(value, W, b, rows=(2 * E, 3 * E))
         if self.training and self.dropout > 0.0:
-            self.last_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))      # torch's CPU generator: no device sync
+            self.last_seed = ops.dropout_seed()      # torch's CPU generator: no device sync (device-RNG mode: a device seed slot)
             o = ops.attention(q, k, v, self.num_heads, attn_mask, self.dropout, self.last_seed)
         else:
             o = ops.attention(q, k, v, self.num_heads, attn_mask)
@@ -149,6 +149,8 @@ class TransformerDecoderLayer(nn.Module):
 
     def _drop(self, t):
         """Inverted dropout with an explicit keep-mask (torch.nn.Dropout semantics: x * mask / keep_prob)."""
+        if ops.device_rng_active():              # capturable step: index-hash mask from a device seed slot (uenc_dropout_sp)
+            return ops.device_dropout(t, self.dropout_p)
         keep = 1.0 - self.dropout_p
         mask = torch.rand(t.shape, device=t.device) < keep
         self._masks.append(mask)

@@ -113,7 +113,9 @@ class OneFormer(nn.Module):
         images = [x["left_image"].to(self.device) for x in seg]
         images = [(x - self.pixel_mean) / self.pixel_std for x in images]
         images = ImageList.from_tensors(images, self.size_divisibility)
-        tasks = torch.cat([self._task_tokens(x["task"]) for x in seg], dim=0)
+        static = getattr(self, "static_task_tokens", None)
+        # a captured step (uenc/graphs.py) reads the token ids from its own device buffer, refilled before a replay
+        tasks = static if static is not None else torch.cat([self._task_tokens(x["task"]) for x in seg], dim=0)
         tasks = self.task_mlp(tasks)
         features = self.backbone(images.tensor)
         outputs, _ = self.sem_seg_head(features, None, tasks)

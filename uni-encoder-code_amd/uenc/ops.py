@@ -167,7 +167,7 @@ class ParamCache:
             for i, (src, dst, rows, cols, tr) in enumerate(pieces):
                 desc[i] = (src, dst, rows, cols, tr, -(-cols // 64), tb)
                 tb += -(-rows // 64) * -(-cols // 64)
-            tab = torch.from_numpy(desc.view(np.uint8).copy()).to(dev) if len(pieces) else None
+            tab = K.upload_table(desc, dev, pinned=False) if len(pieces) else None
             rtab, rblocks = None, 0
             if rel:
                 rdesc = np.zeros(len(rel), dtype=[("table", "<u8"), ("bias_q", "<u8"), ("bias_k", "<u8"), ("nH", "<i4"), ("ws", "<i4"),
@@ -175,7 +175,7 @@ class ParamCache:
                 for i, (tp, bp, nH, ws, NP) in enumerate(rel):
                     rdesc[i] = (tp, bp, 0, nH, ws, NP, rblocks)
                     rblocks += -(-(nH * NP * NP) // 2048)
-                rtab = torch.from_numpy(rdesc.view(np.uint8).copy()).to(dev)
+                rtab = K.upload_table(rdesc, dev, pinned=False)
             keys = (keys, len(pieces))
             self._table = (tab, keys[1], tb, keys[0], rtab, len(rel), rblocks)
         tab, n, total, keys, rtab, rn, rblocks = self._table
@@ -368,8 +368,7 @@ class WgradQueue:
             begin += d[13]
             flops += 2.0 * d[7] * d[8] * d[9]
             nbytes += 2.0 * d[7] * (d[8] + d[9]) + 4.0 * d[8] * d[9]           # bf16 operands read once + the fp32 gradient written once
-        host = torch.from_numpy(desc.view(np.uint8)).pin_memory()
-        tab = host.to(device, non_blocking=True)
+        tab = K.upload_table(desc, device)
         lib.uenc_prof_next_bytes(nbytes)
         check(lib.uenc_gemm_tn_grouped(tab.data_ptr(), len(descs), begin, tile, flops, stream_ptr()), "gemm_tn_grouped")
 
@@ -421,7 +420,7 @@ class WgradQueue:
                 begin += items
                 flops += 2.0 * d[7] * d[8] * d[9]
             dev = self.small[0][2][0].device
-            tab = torch.from_numpy(desc.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+            tab = K.upload_table(desc, dev)
             check(lib.uenc_gemm_tn_grouped_small(tab.data_ptr(), len(self.small), begin, flops, stream_ptr()), "gemm_tn_grouped_small")
             self.small = []
             self.small_items = 0
@@ -481,6 +480,8 @@ def begin_step(fresh_grads: bool = False):
     may then be stored instead of accumulated.  Leave it False when gradients are carried over from earlier backward passes."""
     CACHE.refresh()
     WGRADS.fresh = bool(fresh_grads)
+    if _RNG is not None:
+        _RNG.begin_step()                       # device-RNG mode: this step's DropPath multipliers and dropout seeds
 
 
 def flush_wgrads():
@@ -753,12 +754,173 @@ def layer_norm(x, gamma, beta, *, res=None, out_dtype=F32, eps=1e-5):
 
 
 # --------------------------------------------------------------------------------------------
+# device-side per-step randomness: no host draws, so a step's launches do not depend on per-step host decisions (what a
+# captured, replayed step needs: uenc/graphs.py)
+# --------------------------------------------------------------------------------------------
+class DeviceScales:
+    """The per-sample DropPath multipliers of one residual branch as a device vector (B,) fp32: a row of the step RNG table, written by
+    uenc_step_rng_advance at the start of every step.  Stands where `drop_path_scales` returns python floats otherwise.  owner / gen:
+    the DeviceRNG and its step generation at the draw (`check()` refuses a use after the owner moved on to another step)."""
+    __slots__ = ("vec", "owner", "gen")
+
+    def __init__(self, vec: torch.Tensor, owner=None):
+        self.vec, self.owner = vec, owner
+        self.gen = owner.generation if owner is not None else 0
+
+    def check(self):
+        if self.owner is not None and self.owner.generation != self.gen:
+            raise RuntimeError("device RNG: ops.begin_step() ran between this DropPath branch's forward and its backward -- the table "
+                               "now holds the next step's multipliers")
+
+    def __len__(self):
+        return self.vec.numel()
+
+
+class DeviceRNG:
+    """Device state {base seed, step counter} and the two tables uenc_step_rng_advance writes from it (csrc/step_rng.hip).
+
+    Every DropPath branch and every dropout site of a step claims a slot in call order; `begin_step()` (called by ops.begin_step) resets the
+    order and launches the advance kernel once.  The first step that reaches a slot registers it (its keep probability is uploaded and the
+    tables of the current step are rewritten); no new slot may be registered while a stream is being captured."""
+    MAX_BRANCH = 1024
+    MAX_SEED = 1024
+
+    def __init__(self, seed: int, device=None):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.state = torch.tensor([int(seed) & (2 ** 63 - 1), 0], dtype=torch.int64, device=self.device)
+        self.keep_prob = torch.ones(self.MAX_BRANCH, dtype=F32, device=self.device)
+        self.seeds = torch.zeros(self.MAX_SEED, dtype=torch.int32, device=self.device)
+        self.scales = None                      # (MAX_BRANCH * n_samples,) once the batch size is known
+        self.n_samples = 0
+        self.branch_keep = []                   # keep probability of every registered branch slot, in claim order
+        self.n_seed = 0                         # registered dropout seed slots
+        self._nb = self._ns = 0                 # slots claimed so far in the current step
+        self.generation = 0                     # host count of begin_step() calls (guards backward passes against a later step's tables)
+
+    def _launch(self, advance: bool):
+        nb = len(self.branch_keep) if self.scales is not None else 0
+        K.step_rng_advance(self.state, self.keep_prob, nb, max(self.n_samples, 1), self.scales if nb else self.keep_prob, self.n_seed,
+                           self.seeds, advance)
+
+    def begin_step(self):
+        self._nb = self._ns = 0
+        self.generation += 1
+        self._launch(True)
+
+    def _register(self, what: str):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"device RNG: a new {what} slot was claimed during stream capture -- run one step eagerly first so that every "
+                               "slot is registered")
+
+    def claim_branch(self, B: int, keep: float) -> DeviceScales:
+        i = self._nb
+        self._nb += 1
+        if self.scales is None:
+            self.n_samples = int(B)
+            self.scales = torch.zeros(self.MAX_BRANCH * self.n_samples, dtype=F32, device=self.device)
+        if B != self.n_samples:
+            raise ValueError(f"device RNG: batch size {B} differs from the {self.n_samples} its tables were laid out for")
+        if i == len(self.branch_keep):
+            self._register("DropPath")
+            if i >= self.MAX_BRANCH:
+                raise RuntimeError(f"device RNG: more than {self.MAX_BRANCH} DropPath branches")
+            self.branch_keep.append(float(keep))
+            self.keep_prob[i].fill_(float(keep))
+            self._launch(False)                 # (re)write the current step's tables including the new slot: pure functions of the state
+        elif self.branch_keep[i] != float(keep):
+            raise RuntimeError(f"device RNG: DropPath slot {i} was registered with keep probability {self.branch_keep[i]}, now {keep}")
+        return DeviceScales(self.scales[i * B:(i + 1) * B], self)
+
+    def claim_seed(self) -> K.SeedSlot:
+        j = self._ns
+        self._ns += 1
+        if j == self.n_seed:
+            self._register("dropout seed")
+            if j >= self.MAX_SEED:
+                raise RuntimeError(f"device RNG: more than {self.MAX_SEED} dropout sites")
+            self.n_seed += 1
+            self._launch(False)
+        return K.SeedSlot(self.seeds, j, self)
+
+    def get_state(self) -> torch.Tensor:
+        return self.state.clone()
+
+    def set_state(self, state: torch.Tensor):
+        self.state.copy_(state)
+
+
+_RNG = None
+
+
+class device_rng:
+    """Context manager: DropPath multipliers and dropout seeds come from the device tables of a `DeviceRNG` (uenc_step_rng_advance), no
+    host draws -- the mode a captured training step runs in (uenc/graphs.py); usable eagerly too.  Call `ops.begin_step()` at the start of
+    every step, and not between a forward and its backward: the backward kernels read the tables when they run, so a backward after the
+    next `begin_step()` would see the next step's draws -- it raises instead.  `rng`: an int seed (a new DeviceRNG) or an existing DeviceRNG.  Not available in the fp32 exact mode."""
+
+    def __init__(self, rng):
+        self.rng = rng if isinstance(rng, DeviceRNG) else DeviceRNG(int(rng))
+        self._prev = None
+
+    def __enter__(self) -> DeviceRNG:
+        global _RNG
+        if K.EXACT:
+            raise RuntimeError("ops.device_rng: the fp32 exact mode (UENC_EXACT) has no device-side randomness path")
+        self._prev, _RNG = _RNG, self.rng
+        return self.rng
+
+    def __exit__(self, *exc):
+        global _RNG
+        _RNG = self._prev
+        return False
+
+
+def device_rng_active() -> bool:
+    return _RNG is not None
+
+
+def dropout_seeds(n: int):
+    """n seeds for the index-hash dropout kernels: python ints from torch's CPU generator, or SeedSlots in device-RNG mode."""
+    if _RNG is not None:
+        return tuple(_RNG.claim_seed() for _ in range(n))
+    return tuple(int(v) for v in torch.randint(0, 2 ** 31 - 1, (n,)).tolist())
+
+
+def dropout_seed():
+    """One seed (see dropout_seeds)."""
+    if _RNG is not None:
+        return _RNG.claim_seed()
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)))
+
+
+class DropoutFn(torch.autograd.Function):
+    """Inverted dropout with the index-hash keep mask and a device seed (uenc_dropout_sp): the backward applies the same mask."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        ctx.p, ctx.seed = p, seed
+        return K.dropout_sp(x if x.is_contiguous() else x.contiguous(), seed, p)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return K.dropout_sp(dy if dy.is_contiguous() else dy.contiguous(), ctx.seed, ctx.p), None, None
+
+
+def device_dropout(x: torch.Tensor, p: float) -> torch.Tensor:
+    """nn.Dropout(p) in training mode for device-RNG mode: the mask comes from a claimed seed slot (fp32 / bf16)."""
+    return DropoutFn.apply(x, float(p), _RNG.claim_seed())
+
+
+# --------------------------------------------------------------------------------------------
 # Swin block: LN1 -> qkv -> fused window attention -> proj(+x) -> LN2 -> fc1+GELU -> fc2(+x)
 # --------------------------------------------------------------------------------------------
 def drop_path_scales(B: int, drop_prob: float):
     """timm DropPath (reference backbone/swin.py:8, 231, 279, 289) for one residual branch: per-sample multipliers
-    floor(keep_prob + U[0,1)) / keep_prob as python floats.  Drawn from torch's CPU generator: no device sync."""
+    floor(keep_prob + U[0,1)) / keep_prob as python floats.  Drawn from torch's CPU generator: no device sync.
+    Device-RNG mode: a DeviceScales row of the step's table instead."""
     keep = 1.0 - drop_prob
+    if _RNG is not None:
+        return _RNG.claim_branch(B, keep)
     return [float(v) / keep for v in torch.floor(keep + torch.rand(B)).tolist()]
 
 
@@ -767,6 +929,9 @@ _SCALE_VECS = {}
 
 def _scale_vec(scales, device) -> torch.Tensor:
     """Device copy of a tuple of per-sample DropPath multipliers; cached (a block draws from {0, 1 / keep}^B: few distinct tuples)."""
+    if isinstance(scales, DeviceScales):
+        scales.check()
+        return scales.vec
     key = (tuple(scales), str(device))
     t = _SCALE_VECS.get(key)
     if t is None:
@@ -835,6 +1000,11 @@ def _branch_wgrad(g16, x, gw, gb, notify, scales):
         return
     B = len(scales)
     L = g16.shape[0] // B
+    if isinstance(scales, DeviceScales):
+        scales.check()
+        # multipliers on the device (a replayable step): the scaled gradient rows are materialised once, every row takes part
+        _tn(K.scale_rows_bf16(g16, scales.vec, L), x, gw, gb, notify)
+        return
     runs, b = [], 0
     while b < B:                                       # maximal runs of kept images = contiguous row ranges
         if scales[b] != 0.0:
