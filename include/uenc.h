@@ -414,6 +414,28 @@ int uenc_mha_bwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_b
                     long dk_bs, long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale,
                     float dropout_p, const unsigned* seeds, int slot, uenc_stream_t stream);
 
+/* ---- fused AdamW with full-model gradient clipping (csrc/optim.hip; replaces the reference's optimizer wrapper, tools/calc_throughput.py:
+ * torch.nan_to_num on every gradient, clip_grad_norm_ over all of them, torch.optim.AdamW) ------------------------------------------------
+ * `table` = n device-resident segment descriptors, one per parameter tensor (56 bytes each):
+ *   {float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long n; long tile_begin; int group; int pad;}
+ * tile_begin = exclusive prefix sum of ceil((n + a) / 4096) with a = ((uintptr_t)param / 4) % 4 (tiles start on 16-byte boundaries of the
+ * parameter; gradient and moments may sit at any 4-byte offset); total_tiles = the sum.  All tensors fp32, dense.
+ * `state` = 32-byte device block, 16-byte aligned: {long long step; double norm; float clip_coef, inv_bc1, inv_sqrt_bc2, pad;}.  The caller
+ * initialises it to {steps taken, 0, 1, 0, 0, 0}; nothing a launch computes depends on a value the host read back.
+ * Gradients are sanitised as they are read (NaN -> 0, +inf -> 1e5, -inf -> -1e5) and never written. */
+/* step += 1 and the bias corrections 1 / (1 - beta1^step), 1 / sqrt(1 - beta2^step) of the new step: first launch of an optimizer step. */
+int uenc_optim_advance(void* state, double beta1, double beta2, uenc_stream_t stream);
+/* state.norm = sqrt(sum of squares of all sanitised gradients), state.clip_coef = min(1, max_norm / (norm + 1e-6)).  Two stages without
+ * atomics (per-workgroup partial sums into `partials`, n_partials >= min(total_tiles, 2048) doubles, then one workgroup in a fixed order):
+ * bit-identical from run to run.  Skipped when clipping is off (clip_coef stays 1). */
+int uenc_optim_grad_sqnorm(const void* table, int n, long total_tiles, double* partials, int n_partials, void* state, float max_norm,
+                           uenc_stream_t stream);
+/* torch.optim.AdamW's update (decoupled decay, no amsgrad, no maximize) of every segment with gradient = sanitised * state.clip_coef, at
+ * step count state.step.  `groups` = n_groups x {float lr, weight_decay, 1 - lr * weight_decay, unused} (16-byte aligned device array)
+ * indexed by the segment's group. */
+int uenc_optim_adamw_step(const void* table, int n, long total_tiles, const float* groups, int n_groups, const void* state, double beta1,
+                          double beta2, double eps, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

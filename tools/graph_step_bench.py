@@ -5,6 +5,12 @@ The loss is a capture-safe restatement of bench.synthetic_loss (the same mean sq
 eager steps use the same loss.  Eager train mode draws its randomness on the host, as the product does by default.
 
     python tools/graph_step_bench.py --steps 10 --warmup 3
+
+--optimizer adds the weight update to every leg (eval mode): the eager step followed by the reference's composition on torch
+(nan_to_num per parameter, clip_grad_norm_, torch.optim.AdamW), the eager step followed by uenc.optim.FusedAdamW.step(), and the replay
+of a graph that was captured with the optimizer inside.
+
+    python tools/graph_step_bench.py --steps 10 --warmup 3 --optimizer
 """
 import argparse
 import json
@@ -41,11 +47,50 @@ def _timed(fn, steps):
     return [a.elapsed_time(b) for a, b in evs]
 
 
+def optimizer_legs(args, model, eager_step, images, batch):
+    """Eager step + torch's optimizer, eager step + FusedAdamW, replay with FusedAdamW captured.  The learning rate is tiny so that
+    the weights stay where the timing of the forward / backward was measured."""
+    from uenc.graphs import GraphedTrainStep
+    from uenc.optim import FusedAdamW
+    model.eval()
+    lr, max_norm = 1e-7, 0.01
+    eager_step()                                     # gradients exist; which parameters train is known
+    live = [p for p in model.parameters() if p.requires_grad and p.grad is not None]
+    topt = torch.optim.AdamW(live, lr=lr, weight_decay=0.05, foreach=True)
+
+    def eager_torch():
+        eager_step()
+        for p in live:
+            torch.nan_to_num(p.grad, nan=0.0, posinf=1e5, neginf=-1e5, out=p.grad)
+        torch.nn.utils.clip_grad_norm_(live, max_norm)
+        topt.step()
+    fopt = FusedAdamW(live, lr=lr, weight_decay=0.05, max_grad_norm=max_norm)
+
+    def eager_fused():
+        eager_step()
+        fopt.step()
+    out = {}
+    for name, fn in (("eager_plus_torch_adamw", eager_torch), ("eager_plus_fused_adamw", eager_fused)):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = _stats(_timed(fn, args.steps))
+    del topt
+    gs = GraphedTrainStep(model, loss_fn, batch, warmup=args.warmup, optimizer=fopt)
+    for _ in range(args.warmup):
+        gs.step(images)
+    torch.cuda.synchronize()
+    out["replay_with_optimizer"] = _stats(_timed(lambda: gs.step(images), args.steps))
+    print(json.dumps({"tool": "graph_step_bench", "mode": "eval+optimizer", "workload": "Swin-L OneFormer 1024x2048 bs=%d fwd+bwd+AdamW" % images.shape[0],
+                      "steps": args.steps, "trained_tensors": len(live), "ms": out, "optimizer_steps_on_device": fopt.device_state()["step"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--modes", default="eval,train")
+    ap.add_argument("--optimizer", action="store_true", help="time the step with its weight update (eval mode only)")
     args = ap.parse_args()
 
     import bench
@@ -69,6 +114,10 @@ def main():
         out, _ = model.forward_features(batch)
         loss_fn(out).backward()
         ops.flush_wgrads()
+
+    if args.optimizer:
+        optimizer_legs(args, model, eager_step, images, batch)
+        return
 
     for mode in args.modes.split(","):
         model.train(mode == "train")

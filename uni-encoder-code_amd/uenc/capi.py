@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libuenc_hip.so")
 F32, BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU = range(6)
 
-c_p, c_i, c_l, c_f, c_u = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint
+c_p, c_i, c_l, c_f, c_u, c_d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint, ctypes.c_double
 
 # name -> argtypes; every function returns int unless noted
 _SIGNATURES = {
@@ -101,6 +101,10 @@ _SIGNATURES = {
     "uenc_na2d_f32_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "uenc_na2d_f32_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "uenc_window_attn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
+    # fused AdamW + full-model gradient clipping (csrc/optim.hip)
+    "uenc_optim_advance": [c_p, c_d, c_d, c_p],
+    "uenc_optim_grad_sqnorm": [c_p, c_i, c_l, c_p, c_i, c_p, c_f, c_p],
+    "uenc_optim_adamw_step": [c_p, c_i, c_l, c_p, c_i, c_p, c_d, c_d, c_d, c_p],
 }
 
 

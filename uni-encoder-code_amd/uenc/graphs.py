@@ -10,7 +10,9 @@ depend on host decisions taken per step:
   * inputs -- images and task-token ids live in static device buffers that `step()` refills before the replay.
 
 The captured region: zero the gradients, `ops.begin_step(fresh_grads=True)` (operand re-cast + RNG advance), `model.forward_features`,
-`loss_fn`, backward, the weight-gradient flush.  Post-processing and `upsample_masks` stay outside.  The graph is linear (one stream).
+`loss_fn`, backward, the weight-gradient flush and, when an optimizer is given, its step (uenc.optim.FusedAdamW: step-count advance,
+gradient norm, update -- all of it reads device state only; the per-group learning rates are uploaded by `step()` before the replay).
+Post-processing and `upsample_masks` stay outside.  The graph is linear (one stream).
 """
 from typing import Callable, List, Optional, Sequence
 
@@ -48,13 +50,21 @@ class GraphedTrainStep:
     example_batch: the list of {"left_image", "task", "type": "segmentation"} dicts that fixes the image shape and batch size.
     warmup: eager steps on a side stream before the capture (they also register every randomness slot).
     seed: base seed of the device RNG (train mode).
+    optimizer: a uenc.optim.FusedAdamW over the model's parameters, or None.  With one, every warm-up step and every replay ends with
+    its step; the update leaves the gradients as they are, so after a replay `.grad` holds that step's raw gradients.
 
     step(images, tasks=None) -> (loss, outputs): copies the (B, 3, H, W) images (and, if given, the task prompts) into the static
     buffers, replays, and returns the static loss / output tensors (overwritten by the next replay).  The gradients land in the
     parameters' `.grad` tensors, overwritten at every replay."""
 
-    def __init__(self, model, loss_fn: Callable, example_batch: Sequence[dict], warmup: int = 3, seed: int = 0):
+    def __init__(self, model, loss_fn: Callable, example_batch: Sequence[dict], warmup: int = 3, seed: int = 0, optimizer=None):
         _refuse_unsupported(model)
+        if optimizer is not None:
+            from .optim import FusedAdamW
+            if not isinstance(optimizer, FusedAdamW):
+                raise TypeError(f"GraphedTrainStep: optimizer must be a uenc.optim.FusedAdamW (got {type(optimizer).__name__}); a host-driven "
+                                "optimizer reads learning rates and step counts on the host and cannot be captured")
+        self.optimizer = optimizer
         if not example_batch:
             raise ValueError("GraphedTrainStep: empty example batch")
         for x in example_batch:
@@ -92,6 +102,9 @@ class GraphedTrainStep:
                 self.loss, self.outputs = self._run()
         finally:
             K.CAPTURE_ARENA = None
+        # the graph reads (and, at its start, rewrites) the bf16 operand copies that existed at capture time: they stay allocated even
+        # when the cache replaces an entry (a forward between replays after the weights moved)
+        self._operands = [e[2] for e in ops.CACHE._store.values()]
         torch.cuda.synchronize(self.device)
 
     def _run(self):
@@ -107,6 +120,8 @@ class GraphedTrainStep:
                 loss = self.loss_fn(out)
                 loss.backward()
                 ops.flush_wgrads()
+                if self.optimizer is not None:
+                    self.optimizer.step()
         finally:
             m.static_task_tokens = None
         return loss.detach(), out
@@ -130,5 +145,9 @@ class GraphedTrainStep:
         self.images.copy_(images, non_blocking=True)
         if tasks is not None and list(tasks) != self.tasks:
             self.set_tasks(tasks)
+        if self.optimizer is not None:
+            self.optimizer.sync_groups()        # a scheduler's new learning rates: uploaded outside the graph, like the images
         self.graph.replay()
+        if self.optimizer is not None:
+            self.optimizer.mark_updated()
         return self.loss, self.outputs
