@@ -436,6 +436,29 @@ int uenc_optim_grad_sqnorm(const void* table, int n, long total_tiles, double* p
 int uenc_optim_adamw_step(const void* table, int n, long total_tiles, const float* groups, int n_groups, const void* state, double beta1,
                           double beta2, double eps, uenc_stream_t stream);
 
+/* ---- bipartite matching (csrc/matcher.hip; reference model/modeling/matcher.py) ----------------------------------------------------------
+ * A batch of independent problems, problem = one prediction head of one image.  `probs` is a HOST array of n_prob descriptors which the
+ * call copies into its kernel arguments (no device table; a stream capture records the pointers they hold by value).  Nothing is read
+ * back and nothing synchronises. */
+/* The cost matrix of HungarianMatcher.memory_efficient_forward (matcher.py:126-171) for every problem.  Descriptor (48 bytes):
+ *   {const float* logits (Q, C1); const float* masks (Q, h, w); const float* points (P, 2) x, y in [0, 1]; const unsigned char* gt (T, Hg, Wg)
+ *    0 / 1; const int64* labels (T); int T; int pad;}
+ * Prediction and target are both sampled bilinearly at the P points (point_sample = grid_sample at 2 p - 1, align_corners = False, zero
+ * padding, matcher.py:143-155); cost_mask = (softplus(-x).t + softplus(x).(1 - t)) / P (matcher.py:61-85), cost_dice = 1 - (2 sigmoid(x).t
+ * + 1) / (sum sigmoid(x) + sum t + 1) (matcher.py:38-53), cost_class = -softmax(logits)[:, label] (matcher.py:128-134);
+ * C = w_mask cost_mask + w_class cost_class + w_dice cost_dice (matcher.py:166-170), NaN entries become `nan_fill` (100: matcher.py:33-34; a caller
+ * that wants to see them passes NaN; a label outside [0, C1) counts as NaN).  fp32 throughout, partial sums added in a fixed order: the same input gives the same bits.
+ * `cost` = (n_prob, Q, Tmax) fp32, row stride Tmax; columns >= a problem's T are written as ZERO.  Limits: 1 <= Q, Tmax <= 256,
+ * 0 <= T <= Tmax.  `workspace` = uenc_match_cost_workspace_floats(...) floats, 16-byte aligned; the sampled values stay in LDS. */
+long uenc_match_cost_workspace_floats(int n_prob, int Q, int Tmax, int P);
+int uenc_match_cost(const void* probs, int n_prob, int Q, int C1, int h, int w, int Hg, int Wg, int P, int Tmax, float w_class, float w_mask,
+                    float w_dice, float nan_fill, float* workspace, long workspace_floats, float* cost, uenc_stream_t stream);
+/* scipy.optimize.linear_sum_assignment (matcher.py:36, 173) of every problem's Q x T matrix: shortest augmenting paths with duals in
+ * double, one workgroup per problem.  Descriptor (32 bytes): {const float* cost (Q, ld); int64* row_ind; int64* col_ind; int T; int ld;}.
+ * Writes min(Q, T) pairs in scipy's convention (row_ind ascending, col_ind the matched column); T = 0 writes nothing.  A NaN entry is
+ * read as 100 and entries are clamped to +-1e30, so the search always terminates.  Limits: 1 <= Q <= 256, 0 <= T <= 256, ld >= T. */
+int uenc_lsap_solve(const void* probs, int n_prob, int Q, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

@@ -6,10 +6,17 @@ add_swin_config, add_uni_encoder_config, ...)` and rely on the import side effec
 decoder (model/__init__.py:1-23, model/modeling/__init__.py:1-10).  Putting
 `uni-encoder-code_amd/` on PYTHONPATH gives those drivers this implementation instead.
 """
+import sys as _sys
+
 from uenc.config import *  # noqa: F401,F403
 from uenc.config import __all__ as _cfg_all
 from uenc import modeling  # noqa: F401  (registers backbone / heads / decoder)
 from uenc.oneformer_model import OneFormer  # noqa: F401
 from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55-56 imports it from `model`)
+
+# `model.modeling` IS `uenc.modeling` (one object, also for the import system), so the reference's submodule imports resolve to the
+# product's modules: `from model.modeling.matcher import HungarianMatcher` gives `uenc.modeling.matcher.HungarianMatcher`.
+_sys.modules[__name__ + ".modeling"] = modeling
+_sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
 
 __all__ = list(_cfg_all) + ["OneFormer", "modeling", "InstanceSegEvaluator"]

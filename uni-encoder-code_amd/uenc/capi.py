@@ -105,6 +105,10 @@ _SIGNATURES = {
     "uenc_optim_advance": [c_p, c_d, c_d, c_p],
     "uenc_optim_grad_sqnorm": [c_p, c_i, c_l, c_p, c_i, c_p, c_f, c_p],
     "uenc_optim_adamw_step": [c_p, c_i, c_l, c_p, c_i, c_p, c_d, c_d, c_d, c_p],
+    # matching cost + linear sum assignment (csrc/matcher.hip)
+    "uenc_match_cost_workspace_floats": [c_i, c_i, c_i, c_i],
+    "uenc_match_cost": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p],
+    "uenc_lsap_solve": [c_p, c_i, c_i, c_p],
 }
 
 
@@ -126,6 +130,7 @@ def _load():
     lib.uenc_mha_fwd_workspace_floats.restype = c_l
     lib.uenc_msdeform_attn_bwd_workspace_bytes.restype = c_l
     lib.uenc_groupnorm_tokens_scratch_bytes.restype = c_l
+    lib.uenc_match_cost_workspace_floats.restype = c_l
     lib.uenc_arch.restype = ctypes.c_char_p
     lib.uenc_arch.argtypes = []
     return lib

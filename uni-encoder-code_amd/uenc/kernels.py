@@ -969,3 +969,89 @@ def segment_colsum(x16: torch.Tensor, seg_start: torch.Tensor, rows_per_image: i
     check(lib.uenc_segment_colsum(x16.data_ptr(), x16.stride(0), cols, seg_start.data_ptr(), nseg, rows_per_image, images, out.data_ptr(),
                                   stream_ptr()), "segment_colsum")
     return out.sum(1)
+
+
+# ---- bipartite matching (csrc/matcher.hip) ------------------------------------------------------------------------------------------
+LSAP_MAX = 256                  # LSAP_MAX_N of csrc/matcher.hip: most queries / targets of one problem
+
+
+def _match_dtypes():
+    import numpy as np
+    mp = np.dtype([("logits", "<u8"), ("masks", "<u8"), ("points", "<u8"), ("gt", "<u8"), ("labels", "<u8"), ("T", "<i4"), ("pad", "<i4")])
+    lp = np.dtype([("cost", "<u8"), ("row_ind", "<u8"), ("col_ind", "<u8"), ("T", "<i4"), ("ld", "<i4")])
+    assert mp.itemsize == 48 and lp.itemsize == 32
+    return mp, lp
+
+
+def _dev(t, name: str, dtype, ndim: int):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise capi.UencError(f"{name} must live on the GPU")
+    if t.dtype != dtype or t.dim() != ndim or not t.is_contiguous():
+        raise capi.UencError(f"{name} must be contiguous {dtype} with {ndim} dimensions, got {t.dtype} {tuple(t.shape)} / {t.stride()}")
+    return t
+
+
+def match_cost(problems, w_class: float, w_mask: float, w_dice: float, nan_fill: float = 100.0) -> torch.Tensor:
+    """problems = [(logits (Q, C1) f32, masks (Q, h, w) f32, points (P, 2) f32, gt (T, Hg, Wg) uint8, labels (T) int64), ...], all on one
+    GPU, same Q / C1 / h / w / P / Hg / Wg, any T per problem -> cost (n_prob, Q, Tmax) fp32 with Tmax = max(1, max T); columns >= a
+    problem's T are zero.  One call of uenc_match_cost; the descriptors travel in the kernel arguments."""
+    import numpy as np
+    mp, _ = _match_dtypes()
+    n = len(problems)
+    if n == 0:
+        raise capi.UencError("match_cost: no problems")
+    lg0, mk0, pt0 = problems[0][:3]
+    _dev(lg0, "logits", torch.float32, 2); _dev(mk0, "masks", torch.float32, 3); _dev(pt0, "points", torch.float32, 2)
+    Q, C1 = lg0.shape
+    h, w = mk0.shape[1:]
+    P = pt0.shape[0]
+    Ts = [int(pr[3].shape[0]) for pr in problems]
+    Tmax = max(1, max(Ts))
+    Hg = Wg = 1
+    for pr in problems:
+        if pr[3].shape[0]:
+            Hg, Wg = int(pr[3].shape[1]), int(pr[3].shape[2])
+            break
+    rows = np.zeros(n, dtype=mp)
+    for i, (lg, mk, pt, gt, lab) in enumerate(problems):
+        _dev(lg, "logits", torch.float32, 2); _dev(mk, "masks", torch.float32, 3); _dev(pt, "points", torch.float32, 2)
+        if tuple(lg.shape) != (Q, C1) or tuple(mk.shape) != (Q, h, w) or tuple(pt.shape) != (P, 2):
+            raise capi.UencError("match_cost: every problem of one call must have the same Q, C + 1, h, w and P")
+        if Ts[i]:
+            _dev(gt, "target masks", torch.uint8, 3); _dev(lab, "labels", torch.int64, 1)
+            if tuple(gt.shape[1:]) != (Hg, Wg) or lab.shape[0] != Ts[i]:
+                raise capi.UencError("match_cost: target masks must share one (padded) size and come with one label each")
+        rows[i] = (lg.data_ptr(), mk.data_ptr(), pt.data_ptr(), gt.data_ptr() if Ts[i] else 0, lab.data_ptr() if Ts[i] else 0, Ts[i], 0)
+    nws = lib.uenc_match_cost_workspace_floats(n, Q, Tmax, P)
+    if nws < 0:
+        raise capi.UencError(f"match_cost: Q = {Q} / T = {Tmax} beyond the limit of {LSAP_MAX}, or no points")
+    cost = torch.empty((n, Q, Tmax), dtype=torch.float32, device=lg0.device)
+    ws = torch.empty(nws, dtype=torch.float32, device=lg0.device)
+    check(lib.uenc_match_cost(rows.ctypes.data, n, Q, C1, h, w, Hg, Wg, P, Tmax, w_class, w_mask, w_dice, nan_fill, ws.data_ptr(), nws,
+                              cost.data_ptr(), stream_ptr()), "match_cost")
+    return cost
+
+
+def lsap_solve(cost: torch.Tensor, Ts):
+    """cost (n_prob, Q, ld) fp32 on the GPU, problem p being cost[p, :, :Ts[p]] -> (row_ind, col_ind, offsets): two flat int64 device buffers
+    holding min(Q, Ts[p]) pairs per problem from offsets[p] on (scipy's convention: row_ind ascending).  One call of uenc_lsap_solve, no
+    synchronisation; the offsets are host integers because the shapes are."""
+    import numpy as np
+    _, lp = _match_dtypes()
+    _dev(cost, "cost", torch.float32, 3)
+    n, Q, ld = cost.shape
+    Ts = [int(t) for t in Ts]
+    if len(Ts) != n or n == 0:
+        raise capi.UencError("lsap_solve: one T per problem")
+    if Q < 1 or Q > LSAP_MAX or any(t < 0 or t > LSAP_MAX or t > ld for t in Ts):
+        raise capi.UencError(f"lsap_solve: 1 <= Q <= {LSAP_MAX} and 0 <= T <= min({LSAP_MAX}, row stride) are required, got Q = {Q}, T = {Ts}")
+    offs = [0]
+    for t in Ts:
+        offs.append(offs[-1] + min(Q, t))
+    out = torch.empty((2, max(offs[-1], 1)), dtype=torch.int64, device=cost.device)
+    rows = np.zeros(n, dtype=lp)
+    base, rp, cp = cost.data_ptr(), out[0].data_ptr(), out[1].data_ptr()
+    for i, t in enumerate(Ts):
+        rows[i] = (base + 4 * i * Q * ld, rp + 8 * offs[i], cp + 8 * offs[i], t, ld)
+    check(lib.uenc_lsap_solve(rows.ctypes.data, n, Q, stream_ptr()), "lsap_solve")
+    return out[0], out[1], offs
