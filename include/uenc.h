@@ -459,6 +459,38 @@ int uenc_match_cost(const void* probs, int n_prob, int Q, int C1, int h, int w, 
  * read as 100 and entries are clamped to +-1e30, so the search always terminates.  Limits: 1 <= Q <= 256, 0 <= T <= 256, ld >= T. */
 int uenc_lsap_solve(const void* probs, int n_prob, int Q, uenc_stream_t stream);
 
+/* ---- MonodepthLoss hot path (csrc/monodepth.hip; reference model/modeling/monodepth_loss.py:427-517, 671-680, 734-777) ---------------------
+ * fp32, dense tensors, S <= 4 scales (scale s is (H >> s) x (W >> s); H and W divisible by 2^(S-1)), NF <= 2 source frames, no float atomics:
+ * the same input gives the same bits.  `desc` is a HOST block of 67 pointers which the call copies into its kernel arguments (a stream
+ * capture records them by value), index = scale * NF + frame where two are given:
+ *   const float* disp[4] (B, 1, h, w); cflow[8] (B, 3, h, w); mask[8] (B, 1, h, w); T (NF, B, 4, 4); K (B, 4, 4); invK (B, 4, 4);
+ *   src (NF, B, 3, H, W);
+ *   float* color (S, NF, B, 3, H, W); sample (S, NF, B, H, W, 2); sample_ego; sample_cmp (as sample); depth (S, B, 1, H, W);
+ *   residual[8] (B, 3, H, W);
+ *   const float* gcolor (as color); gres[8] (as residual, NULL = zero);
+ *   float* gdisp[4]; gcflow[8]; gmask[8] (as their inputs); gT (NF, B, 4, 4).
+ * mode 0: rigid (sample = K T depth invK pix); 1: complete flow only (sample = K (X + flow)); 2: complete flow with the motion mask
+ * (sample = K T (X + (flow - ego) mask)); modes 1 and 2 also write sample_ego, sample_cmp and residual = flow - ego at full resolution.
+ * Per pixel: disp upsampled bilinearly (align_corners = False), depth = 1 / (0.01 + 9.99 disp), projection divided by z + 1e-7 and
+ * normalised by (W - 1, H - 1), colour sampled with border padding and align_corners = True. */
+int uenc_view_synth_fwd(const void* desc, int S, int NF, int B, int H, int W, int mode, uenc_stream_t stream);
+/* Gradients of (gcolor, gres) to disp, cam_T_cam, complete flow and motion mask; every output element is written.  Two launches: per
+ * full-resolution pixel into `workspace` (with per-block partial sums for cam_T_cam), then one gather per low-resolution pixel over its
+ * bounded footprint and the partials added in a fixed order.  `workspace` = uenc_view_synth_workspace_floats(...) floats. */
+long uenc_view_synth_workspace_floats(int S, int NF, int B, int H, int W);
+int uenc_view_synth_bwd(const void* desc, int S, int NF, int B, int H, int W, int mode, float* workspace, long workspace_floats,
+                        uenc_stream_t stream);
+/* Per pixel and candidate 0.85 mean_c SSIM + 0.15 mean_c L1 against `target` (B, 3, H, W); SSIM = clamp((1 - ssim) / 2, 0, 1) over 3x3
+ * means of the reflection-padded images, C1 = 1e-4, C2 = 9e-4.  Candidates: the NF warped frames color[s][f]; with automask = 1 the NF
+ * source frames src (NF, B, 3, H, W) come first, each plus noise (S, B, NF, H, W) * 1e-5.  argmin (S, B, H, W) = index of the smallest
+ * (the first on a tie), p_photo[s] = mean of the minimum over B * H * W (block partials in `workspace`, added in a fixed order). */
+long uenc_photo_loss_workspace_floats(int S, int B, int H, int W);
+int uenc_photo_loss_fwd(const float* color, const float* target, const float* src, const float* noise, int S, int NF, int B, int H, int W,
+                        int automask, float* workspace, long workspace_floats, unsigned char* argmin, float* p_photo, uenc_stream_t stream);
+/* grad_color (as color) = d(sum_s grad_p_photo[s] p_photo[s]) / d(color): through the selected candidate only, zero elsewhere. */
+int uenc_photo_loss_bwd(const float* color, const float* target, const unsigned char* argmin, const float* grad_p_photo, int S, int NF, int B,
+                        int H, int W, int automask, float* grad_color, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

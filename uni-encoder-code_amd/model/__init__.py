@@ -18,5 +18,6 @@ from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55
 # product's modules: `from model.modeling.matcher import HungarianMatcher` gives `uenc.modeling.matcher.HungarianMatcher`.
 _sys.modules[__name__ + ".modeling"] = modeling
 _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
+_sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
 
 __all__ = list(_cfg_all) + ["OneFormer", "modeling", "InstanceSegEvaluator"]

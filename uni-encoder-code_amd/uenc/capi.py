@@ -109,6 +109,13 @@ _SIGNATURES = {
     "uenc_match_cost_workspace_floats": [c_i, c_i, c_i, c_i],
     "uenc_match_cost": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p],
     "uenc_lsap_solve": [c_p, c_i, c_i, c_p],
+    # view synthesis + photometric loss of MonodepthLoss (csrc/monodepth.hip)
+    "uenc_view_synth_workspace_floats": [c_i, c_i, c_i, c_i, c_i],
+    "uenc_view_synth_fwd": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_view_synth_bwd": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p],
+    "uenc_photo_loss_workspace_floats": [c_i, c_i, c_i, c_i],
+    "uenc_photo_loss_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p],
+    "uenc_photo_loss_bwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
 }
 
 
@@ -131,6 +138,8 @@ def _load():
     lib.uenc_msdeform_attn_bwd_workspace_bytes.restype = c_l
     lib.uenc_groupnorm_tokens_scratch_bytes.restype = c_l
     lib.uenc_match_cost_workspace_floats.restype = c_l
+    lib.uenc_view_synth_workspace_floats.restype = c_l
+    lib.uenc_photo_loss_workspace_floats.restype = c_l
     lib.uenc_arch.restype = ctypes.c_char_p
     lib.uenc_arch.argtypes = []
     return lib

@@ -1055,3 +1055,138 @@ def lsap_solve(cost: torch.Tensor, Ts):
         rows[i] = (base + 4 * i * Q * ld, rp + 8 * offs[i], cp + 8 * offs[i], t, ld)
     check(lib.uenc_lsap_solve(rows.ctypes.data, n, Q, stream_ptr()), "lsap_solve")
     return out[0], out[1], offs
+
+
+# ---- MonodepthLoss: view synthesis + photometric loss (csrc/monodepth.hip) -----------------------------------------------------------------
+# slots of the 67-pointer descriptor of uenc_view_synth_fwd / _bwd (struct VsDesc)
+_VS = {"disp": 0, "cflow": 4, "mask": 12, "T": 20, "K": 21, "invK": 22, "src": 23, "color": 24, "sample": 25, "sample_ego": 26, "sample_cmp": 27,
+       "depth": 28, "residual": 29, "gcolor": 37, "gres": 38, "gdisp": 46, "gcflow": 50, "gmask": 58, "gT": 66}
+_VS_SLOTS = 67
+
+
+def _vs_desc(mode, K, inv_K, src, T, disps, cflows, masks):
+    """Checks the inputs of one view-synthesis call and fills the input slots -> (descriptor, S, NF, B, H, W)."""
+    import numpy as np
+    _dev(src, "src", torch.float32, 5)
+    NF, B, _, H, W = src.shape
+    S = len(disps)
+    if not (1 <= S <= 4 and 1 <= NF <= 2) or src.shape[2] != 3 or mode not in (0, 1, 2):
+        raise capi.UencError("view_synth: 1..4 scales, 1..2 source frames of 3 channels, mode 0 / 1 / 2")
+    _dev(K, "K", torch.float32, 3); _dev(inv_K, "inv_K", torch.float32, 3); _dev(T, "cam_T_cam", torch.float32, 4)
+    if tuple(K.shape) != (B, 4, 4) or tuple(inv_K.shape) != (B, 4, 4) or tuple(T.shape) != (NF, B, 4, 4):
+        raise capi.UencError("view_synth: K / inv_K (B, 4, 4) and cam_T_cam (NF, B, 4, 4) are required")
+    d = np.zeros(_VS_SLOTS, dtype=np.uint64)
+    d[_VS["T"]], d[_VS["K"]], d[_VS["invK"]], d[_VS["src"]] = T.data_ptr(), K.data_ptr(), inv_K.data_ptr(), src.data_ptr()
+    for s in range(S):
+        if (H >> s) << s != H or (W >> s) << s != W:
+            raise capi.UencError(f"view_synth: {H} x {W} is not divisible by 2^{s}")
+        shape = (B, 1, H >> s, W >> s)
+        if tuple(_dev(disps[s], "disp", torch.float32, 4).shape) != shape:
+            raise capi.UencError(f"view_synth: disp of scale {s} must be {shape}")
+        d[_VS["disp"] + s] = disps[s].data_ptr()
+        for f in range(NF):
+            if mode >= 1:
+                if tuple(_dev(cflows[s * NF + f], "complete_flow", torch.float32, 4).shape) != (B, 3, H >> s, W >> s):
+                    raise capi.UencError(f"view_synth: complete_flow of scale {s} must be {(B, 3, H >> s, W >> s)}")
+                d[_VS["cflow"] + s * NF + f] = cflows[s * NF + f].data_ptr()
+            if mode >= 2:
+                if tuple(_dev(masks[s * NF + f], "motion_mask", torch.float32, 4).shape) != shape:
+                    raise capi.UencError(f"view_synth: motion_mask of scale {s} must be {shape}")
+                d[_VS["mask"] + s * NF + f] = masks[s * NF + f].data_ptr()
+    return d, S, NF, B, H, W
+
+
+def view_synth_fwd(mode: int, K, inv_K, src, T, disps, cflows=None, masks=None):
+    """One uenc_view_synth_fwd launch for all scales, source frames and images -> {"color" (S, NF, B, 3, H, W), "sample" (S, NF, B, H, W, 2),
+    "depth" (S, B, 1, H, W)} and for mode >= 1 {"sample_ego", "sample_complete", "residual": S * NF tensors (B, 3, H, W)}."""
+    d, S, NF, B, H, W = _vs_desc(mode, K, inv_K, src, T, disps, cflows, masks)
+    dev = src.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"color": new(S, NF, B, 3, H, W), "sample": new(S, NF, B, H, W, 2), "depth": new(S, B, 1, H, W)}
+    d[_VS["color"]], d[_VS["sample"]], d[_VS["depth"]] = out["color"].data_ptr(), out["sample"].data_ptr(), out["depth"].data_ptr()
+    if mode >= 1:
+        out["sample_ego"], out["sample_complete"] = new(S, NF, B, H, W, 2), new(S, NF, B, H, W, 2)
+        out["residual"] = [new(B, 3, H, W) for _ in range(S * NF)]
+        d[_VS["sample_ego"]], d[_VS["sample_cmp"]] = out["sample_ego"].data_ptr(), out["sample_complete"].data_ptr()
+        for i, r in enumerate(out["residual"]):
+            d[_VS["residual"] + i] = r.data_ptr()
+    check(lib.uenc_view_synth_fwd(d.ctypes.data, S, NF, B, H, W, mode, stream_ptr()), "view_synth_fwd")
+    return out
+
+
+def view_synth_bwd(mode: int, K, inv_K, src, T, disps, cflows, masks, gcolor, gres=None):
+    """-> (d cam_T_cam (NF, B, 4, 4), [d disp], [d complete_flow] or None, [d motion_mask] or None) from d color and, for mode >= 1, the S * NF
+    d residual tensors (None = zero).  Two launches, no atomics."""
+    d, S, NF, B, H, W = _vs_desc(mode, K, inv_K, src, T, disps, cflows, masks)
+    dev = src.device
+    gcolor = _dev(gcolor.contiguous(), "grad color", torch.float32, 6)
+    if tuple(gcolor.shape) != (S, NF, B, 3, H, W):
+        raise capi.UencError("view_synth_bwd: grad color must be (S, NF, B, 3, H, W)")
+    d[_VS["gcolor"]] = gcolor.data_ptr()
+    keep = [gcolor]
+    if mode >= 1 and gres is not None:
+        for i, g in enumerate(gres):
+            if g is not None:
+                g = _dev(g.contiguous(), "grad residual", torch.float32, 4)
+                if tuple(g.shape) != (B, 3, H, W):
+                    raise capi.UencError("view_synth_bwd: grad residual must be (B, 3, H, W)")
+                keep.append(g)
+                d[_VS["gres"] + i] = g.data_ptr()
+    gT = torch.empty((NF, B, 4, 4), dtype=torch.float32, device=dev)
+    gdisp = [torch.empty_like(t) for t in disps]
+    gcf = [torch.empty_like(t) for t in cflows] if mode >= 1 else None
+    gmask = [torch.empty_like(t) for t in masks] if mode >= 2 else None
+    d[_VS["gT"]] = gT.data_ptr()
+    for s in range(S):
+        d[_VS["gdisp"] + s] = gdisp[s].data_ptr()
+    for i in range(S * NF):
+        if mode >= 1:
+            d[_VS["gcflow"] + i] = gcf[i].data_ptr()
+        if mode >= 2:
+            d[_VS["gmask"] + i] = gmask[i].data_ptr()
+    nws = lib.uenc_view_synth_workspace_floats(S, NF, B, H, W)
+    if nws < 0:
+        raise capi.UencError("view_synth_bwd: shape beyond the kernel's limits")
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    check(lib.uenc_view_synth_bwd(d.ctypes.data, S, NF, B, H, W, mode, ws.data_ptr(), nws, stream_ptr()), "view_synth_bwd")
+    return gT, gdisp, gcf, gmask
+
+
+def _photo_shapes(color, target):
+    _dev(color, "color", torch.float32, 6); _dev(target, "target", torch.float32, 4)
+    S, NF, B, C, H, W = color.shape
+    if C != 3 or tuple(target.shape) != (B, 3, H, W):
+        raise capi.UencError("photo_loss: color (S, NF, B, 3, H, W) and target (B, 3, H, W) are required")
+    return S, NF, B, H, W
+
+
+def photo_loss_fwd(color, target, src=None, noise=None):
+    """-> (p_photo (S,), argmin (S, B, H, W) uint8).  `noise` (S, B, NF, H, W) switches auto-masking on: the source frames `src`
+    (NF, B, 3, H, W) plus noise * 1e-5 are candidates 0 .. NF - 1, the warped frames follow."""
+    S, NF, B, H, W = _photo_shapes(color, target)
+    automask = int(noise is not None)
+    if automask:
+        _dev(src, "src", torch.float32, 5); _dev(noise, "noise", torch.float32, 5)
+        if tuple(src.shape) != (NF, B, 3, H, W) or tuple(noise.shape) != (S, B, NF, H, W):
+            raise capi.UencError("photo_loss: src (NF, B, 3, H, W) and noise (S, B, NF, H, W) are required for auto-masking")
+    nws = lib.uenc_photo_loss_workspace_floats(S, B, H, W)
+    if nws < 0:
+        raise capi.UencError("photo_loss: shape beyond the kernel's limits")
+    ws = torch.empty(nws, dtype=torch.float32, device=color.device)
+    arg = torch.empty((S, B, H, W), dtype=torch.uint8, device=color.device)
+    p = torch.empty(S, dtype=torch.float32, device=color.device)
+    check(lib.uenc_photo_loss_fwd(color.data_ptr(), target.data_ptr(), ptr(src) if automask else 0, ptr(noise), S, NF, B, H, W, automask,
+                                  ws.data_ptr(), nws, arg.data_ptr(), p.data_ptr(), stream_ptr()), "photo_loss_fwd")
+    return p, arg
+
+
+def photo_loss_bwd(color, target, argmin, grad_p, automask: bool):
+    """d(sum_s grad_p[s] p_photo[s]) / d color, shaped as color."""
+    S, NF, B, H, W = _photo_shapes(color, target)
+    _dev(argmin, "argmin", torch.uint8, 4); _dev(grad_p, "grad p_photo", torch.float32, 1)
+    if tuple(argmin.shape) != (S, B, H, W) or grad_p.shape[0] != S:
+        raise capi.UencError("photo_loss_bwd: argmin (S, B, H, W) and grad (S,) are required")
+    g = torch.empty_like(color)
+    check(lib.uenc_photo_loss_bwd(color.data_ptr(), target.data_ptr(), argmin.data_ptr(), grad_p.data_ptr(), S, NF, B, H, W, int(automask),
+                                  g.data_ptr(), stream_ptr()), "photo_loss_bwd")
+    return g
