@@ -491,6 +491,33 @@ int uenc_photo_loss_fwd(const float* color, const float* target, const float* sr
 int uenc_photo_loss_bwd(const float* color, const float* target, const unsigned char* argmin, const float* grad_p_photo, int S, int NF, int B,
                         int H, int W, int automask, float* grad_color, uenc_stream_t stream);
 
+/* ---- ConvNeXt block front end (csrc/dwconv.hip; reference model/modeling/backbone/convnext.py:32-33, 43-45) ------------------------------
+ * 7x7 depthwise convolution (stride 1, zero padding 3) on a channels-last fp32 map, fused with the LayerNorm over channels that follows:
+ *   y = dwconv7x7(x) + b,  h = LN_C(y) * gamma + beta.   x, y (B, H, W, C) fp32; w (C, 1, 7, 7) fp32; b (C) or NULL; h fp32 | bf16
+ * (h_dtype); stats (B*H*W, 2) = (mean, rstd).  All arithmetic fp32.  C % 8 == 0, C <= 6144, B <= 65535; any H, W >= 1 (maps smaller than
+ * the filter included); x, y, stats 16-byte aligned.  One launch: 8 x 8 pixel tiles, channels in slabs of 32 through a 25 KB LDS halo. */
+int uenc_dwconv7_ln_fwd(const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* y, void* h, int h_dtype,
+                        float* stats, int B, int H, int W, int C, float eps, uenc_stream_t stream);
+/* dy = LN'(dh) per pixel from the saved y / stats (dgamma, dbeta, part_ws, defer_param_sums exactly as for uenc_layernorm_bwd, rows
+ * M = B*H*W), then dx = dwconv7x7^T(dy) [+ dout]: correlation with the flipped filter, same padding.  dh fp32 | bf16; dout NULL or the
+ * (B, H, W, C) fp32 gradient arriving on the block's skip path; dy, dx (B, H, W, C) fp32, every element written, dy != dx.  dy is the
+ * operand of uenc_dwconv7_bwd_weight.  Two launches. */
+int uenc_dwconv7_ln_bwd_data(const void* dh, int dh_dtype, const float* y, const float* stats, const float* gamma, const float* w,
+                             const float* dout, float* dy, float* dx, float* dgamma, float* dbeta, float* part_ws, int defer_param_sums,
+                             int B, int H, int W, int C, uenc_stream_t stream);
+/* dw[c][ky][kx] += sum_{b,y,x} dy[b][y][x][c] * x[b][y+ky-3][x+kx-3][c], db[c] += sum dy (db may be NULL).  No atomics: per-workgroup
+ * partials are stored to `workspace` (uenc_dwconv7_bwd_weight_workspace_bytes(), 16-byte aligned) and added in a fixed order, so the
+ * same inputs give the same bits. */
+long uenc_dwconv7_bwd_weight_workspace_bytes(int B, int H, int W, int C);
+int uenc_dwconv7_bwd_weight(const float* dy, const float* x, float* dw, float* db, void* workspace, long workspace_bytes, int B, int H, int W,
+                            int C, uenc_stream_t stream);
+/* Layer scale folded into a Linear (convnext.py:48-50: gamma * (W2 g + b2) run as W2' = gamma (.) W2 row-wise, b2' = gamma (.) b2).
+ * From the folded layer's gradients dW2' (N, K), db2' (N, may be NULL):
+ *   gW2 += gamma (.) dW2',  gb2 += gamma (.) db2',  ggamma[n] += sum_k dW2'[n][k] W2[n][k] + db2'[n] b2[n].
+ * gW2 / gb2 / ggamma may each be NULL (frozen parameter); b2 NULL = no bias.  Fixed summation order. */
+int uenc_layer_scale_grads(const float* dw2p, const float* db2p, const float* w2, const float* b2, const float* gamma, float* gw2, float* gb2,
+                           float* ggamma, int N, int K, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

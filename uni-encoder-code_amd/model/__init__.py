@@ -19,5 +19,7 @@ from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55
 _sys.modules[__name__ + ".modeling"] = modeling
 _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
+_sys.modules[__name__ + ".modeling.backbone"] = modeling.backbone
+_sys.modules[__name__ + ".modeling.backbone.convnext"] = modeling.backbone.convnext
 
 __all__ = list(_cfg_all) + ["OneFormer", "modeling", "InstanceSegEvaluator"]

@@ -116,6 +116,12 @@ _SIGNATURES = {
     "uenc_photo_loss_workspace_floats": [c_i, c_i, c_i, c_i],
     "uenc_photo_loss_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p],
     "uenc_photo_loss_bwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
+    # ConvNeXt block: 7x7 depthwise convolution + LayerNorm, its backward kernels, layer-scale gradients (csrc/dwconv.hip)
+    "uenc_dwconv7_ln_fwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
+    "uenc_dwconv7_ln_bwd_data": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_dwconv7_bwd_weight_workspace_bytes": [c_i, c_i, c_i, c_i],
+    "uenc_dwconv7_bwd_weight": [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p],
+    "uenc_layer_scale_grads": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
 }
 
 
@@ -140,6 +146,7 @@ def _load():
     lib.uenc_match_cost_workspace_floats.restype = c_l
     lib.uenc_view_synth_workspace_floats.restype = c_l
     lib.uenc_photo_loss_workspace_floats.restype = c_l
+    lib.uenc_dwconv7_bwd_weight_workspace_bytes.restype = c_l
     lib.uenc_arch.restype = ctypes.c_char_p
     lib.uenc_arch.argtypes = []
     return lib

@@ -117,7 +117,8 @@ def add_dinat_config(cfg):
 
 
 def add_convnext_config(cfg):
-    """ConvNeXt backbone keys (model/config.py: add_convnext_config); the backbone itself is out of scope."""
+    """ConvNeXt backbone keys (model/config.py: add_convnext_config), read by `D2ConvNeXt` (uenc/modeling/backbone/convnext.py):
+    the ConvNeXt-L defaults of the reference."""
     _apply(cfg, [("MODEL.CONVNEXT.IN_CHANNELS", 3), ("MODEL.CONVNEXT.DEPTHS", [3, 3, 27, 3]),
                  ("MODEL.CONVNEXT.DIMS", [192, 384, 768, 1536]), ("MODEL.CONVNEXT.DROP_PATH_RATE", 0.4),
                  ("MODEL.CONVNEXT.LSIT", 1.0), ("MODEL.CONVNEXT.OUT_INDICES", [0, 1, 2, 3]),

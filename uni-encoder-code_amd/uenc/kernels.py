@@ -1190,3 +1190,69 @@ def photo_loss_bwd(color, target, argmin, grad_p, automask: bool):
     check(lib.uenc_photo_loss_bwd(color.data_ptr(), target.data_ptr(), argmin.data_ptr(), grad_p.data_ptr(), S, NF, B, H, W, int(automask),
                                   g.data_ptr(), stream_ptr()), "photo_loss_bwd")
     return g
+
+
+# ---- ConvNeXt block: 7x7 depthwise convolution + LayerNorm (csrc/dwconv.hip) ----
+def _dw_check(x: torch.Tensor, name: str):
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise capi.UencError(f"{name} must be a contiguous (B, H, W, C) fp32 GPU tensor, got {tuple(x.shape)} {x.dtype}")
+    if x.shape[-1] % 8 != 0:
+        raise ValueError(f"the depthwise-convolution kernels need a channel count that is a multiple of 8 (got {x.shape[-1]}); every "
+                         "stock ConvNeXt width satisfies this")
+    return x.shape
+
+
+def dwconv7_ln_fwd(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-6):
+    """x (B, H, W, C) fp32 channels-last, w (C, 1, 7, 7), b (C) -> (y = dwconv7x7(x) + b in fp32, h = LN_C(y) in the GEMM operand dtype
+    (bf16; fp32 in exact mode), stats (B*H*W, 2) = (mean, rstd))."""
+    B, H, W, C = _dw_check(x, "x")
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == 49 * C and (b is None or (b.dtype == torch.float32 and b.numel() == C))
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == C and beta.numel() == C
+    y = torch.empty_like(x)
+    h = torch.empty(x.shape, dtype=adt(), device=x.device)
+    stats = torch.empty((B * H * W, 2), dtype=torch.float32, device=x.device)
+    check(lib.uenc_dwconv7_ln_fwd(x.data_ptr(), w.data_ptr(), ptr(b), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), h.data_ptr(), dt(h),
+                                  stats.data_ptr(), B, H, W, C, float(eps), stream_ptr()), "dwconv7_ln_fwd")
+    return y, h, stats
+
+
+def dwconv7_ln_bwd_data(dh: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor, w: torch.Tensor, *,
+                        dout: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
+                        defer: Optional["SmallReductions"] = None):
+    """-> (dx, dy): dy = LN'(dh) per pixel (fp32, the weight-gradient kernel's operand), dx = dwconv7x7^T(dy) [+ dout].  dh in the operand
+    dtype, dout the fp32 gradient of the block's skip path; the LayerNorm's dgamma / dbeta are accumulated in place (`defer`: as in
+    layernorm_bwd)."""
+    B, H, W, C = _dw_check(y, "y")
+    assert dh.is_contiguous() and dh.numel() == y.numel() and dh.is_cuda and w.is_contiguous() and w.numel() == 49 * C
+    if dout is not None:
+        assert dout.dtype == torch.float32 and dout.is_contiguous() and dout.numel() == y.numel()
+    dy, dx = torch.empty_like(y), torch.empty_like(y)
+    part, deferred = _ln_part(B * H * W, C, dgamma, dbeta, y.device, defer)
+    check(lib.uenc_dwconv7_ln_bwd_data(dh.data_ptr(), dt(dh), y.data_ptr(), stats.data_ptr(), gamma.data_ptr(), w.data_ptr(), ptr(dout),
+                                       dy.data_ptr(), dx.data_ptr(), ptr(dgamma), ptr(dbeta), ptr(part), int(deferred), B, H, W, C,
+                                       stream_ptr()), "dwconv7_ln_bwd_data")
+    return dx, dy
+
+
+def dwconv7_bwd_weight(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor] = None):
+    """dw (C, 1, 7, 7) += correlation of dy with x over all pixels, db (C) += sum of dy; two stages, fixed summation order."""
+    B, H, W, C = _dw_check(x, "x")
+    _dw_check(dy, "dy")
+    assert dy.shape == x.shape and dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == 49 * C
+    assert db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == C)
+    nbytes = int(lib.uenc_dwconv7_bwd_weight_workspace_bytes(B, H, W, C))
+    ws = _scratch("dwconv_wgrad", nbytes, x.device)
+    check(lib.uenc_dwconv7_bwd_weight(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), ptr(db), ws.data_ptr(), ws.numel(), B, H, W, C, stream_ptr()),
+          "dwconv7_bwd_weight")
+
+
+def layer_scale_grads(dw2p: torch.Tensor, db2p: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor], gamma: torch.Tensor,
+                      gw2: Optional[torch.Tensor], gb2: Optional[torch.Tensor], ggamma: Optional[torch.Tensor]):
+    """Gradients of W2, b2, gamma from those of the folded layer W2' = gamma (.) W2, b2' = gamma (.) b2 (accumulated in place)."""
+    N, Kd = w2.shape
+    for t in (dw2p, w2, gw2):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (N, Kd))
+    for t in (db2p, b2, gamma, gb2, ggamma):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N)
+    check(lib.uenc_layer_scale_grads(dw2p.data_ptr(), ptr(db2p), w2.data_ptr(), ptr(b2), gamma.data_ptr(), ptr(gw2), ptr(gb2), ptr(ggamma),
+                                     N, Kd, stream_ptr()), "layer_scale_grads")

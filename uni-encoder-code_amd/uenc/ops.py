@@ -117,6 +117,17 @@ class ParamCache:
     def catvec(self, p1: torch.Tensor, p2: torch.Tensor) -> torch.Tensor:
         return self._get2(p1, p2, "catv", lambda: torch.cat([p1.detach(), p2.detach()]).float().contiguous())
 
+    def scaled(self, w: torch.Tensor, gamma: torch.Tensor, transposed: bool = False) -> torch.Tensor:
+        """Operand of a Linear with layer scale folded in: gamma (.) W row-wise, (N, K), or its (K, N) transpose.  Derived from two
+        masters, so it is re-made when either changed (after an optimizer step) instead of by the batched refresh."""
+        def make():
+            ws = (w.detach().reshape(w.shape[0], -1) * gamma.detach().view(-1, 1)).contiguous()
+            return K.cast_transpose_bf16(ws) if transposed else K.cast_bf16(ws)
+        return self._get2(w, gamma, "lsT" if transposed else "ls", make)
+
+    def scaled_vec(self, b: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+        return self._get2(b, gamma, "lsv", lambda: (b.detach() * gamma.detach()).float().contiguous())
+
     def vec16(self, p: torch.Tensor) -> torch.Tensor:
         return self._get(p, "v", lambda: K.cast_bf16(p.detach().contiguous()), None if K.EXACT else (0, 1, p.numel(), 0))
 
@@ -278,6 +289,7 @@ class WgradQueue:
         self.small = []                          # descriptors for the register-staged kernel (small / fp32-operand problems)
         self.small_items = 0
         self.notify = []
+        self.post = []                           # steps that read a queued group's result (layer-scale gradients): run by flush()
         self.callback_armed = False
         self.enabled = True
         self.written = set()                     # data_ptr of gradient buffers that received a contribution this step
@@ -332,7 +344,7 @@ class WgradQueue:
                 pass
 
     def busy(self) -> bool:
-        return bool(self.notify or self.items[256] or self.items[128] or self.small_items or SMALLQ)
+        return bool(self.notify or self.post or self.items[256] or self.items[128] or self.small_items or SMALLQ)
 
     def add(self, dy, x, gw, gb, notify=(), first=False, alpha: float = 1.0):
         M, N, Kd = dy.shape[0], dy.shape[1], x.shape[1]
@@ -381,7 +393,7 @@ class WgradQueue:
         `callback_armed` would stay set and the stale groups would be launched -- a step late -- with the next pass)."""
         self.pending = {256: [], 128: []}
         self.items = {256: 0, 128: 0}
-        self.small, self.small_items, self.notify = [], 0, []
+        self.small, self.small_items, self.notify, self.post = [], 0, [], []
         SMALLQ.clear()
         self.callback_armed = False
         self.written = set()
@@ -400,7 +412,8 @@ class WgradQueue:
         return first
 
     def flush(self):
-        """Launch everything queued (both tile classes), then release the held gradient-ready notifications."""
+        """Launch everything queued (both tile classes), run the steps that wait for those results, then release the held
+        gradient-ready notifications."""
         self.stores = {}
         for tile in (256, 128):
             ent = self.pending[tile]
@@ -426,6 +439,10 @@ class WgradQueue:
             self.small_items = 0
         if SMALLQ:
             SMALLQ.flush()                      # parked LayerNorm / position-table partial sums: one grouped launch per kind
+        if self.post:
+            post, self.post = self.post, []
+            for fn in post:
+                fn()
         if self.notify:
             params, self.notify = self.notify, []
             _notify(*params)
@@ -495,6 +512,19 @@ def _tn_notify(*params):
         WGRADS.notify.extend(p for p in params if p is not None)
     else:
         _notify(*params)
+
+
+def _after_wgrads(fn, notify=()):
+    """Run `fn` once every weight-gradient GEMM issued so far has been launched (now, or in the queue's flush), then release `notify`."""
+    if not WGRADS.busy():
+        fn()
+        _notify(*notify)
+        return
+    WGRADS.post.append(fn)
+    WGRADS.notify.extend(p for p in notify if p is not None)
+    WGRADS._arm()
+    if not WGRADS.callback_armed:
+        WGRADS.flush()
 
 
 def _tn(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: Optional[torch.Tensor], notify=(), alpha: float = 1.0):
@@ -1787,3 +1817,147 @@ class PatchMergeLnFn(torch.autograd.Function):
 
 def patch_merge_ln(x_bhwc, gamma, beta, eps: float = 1e-5):
     return PatchMergeLnFn.apply(x_bhwc, gamma, beta, eps)
+
+
+# --------------------------------------------------------------------------------------------
+# ConvNeXt block: dwconv 7x7 + LN -> fc1 + GELU -> fc2 (layer scale folded in) (+x)
+# --------------------------------------------------------------------------------------------
+class ConvNeXtBlockFn(torch.autograd.Function):
+    """One whole ConvNeXt Block (reference backbone/convnext.py:41-54) as 3 kernels forward: the fused depthwise convolution +
+    LayerNorm (csrc/dwconv.hip), fc1 + GELU, fc2 with the residual epilogue.  x is the fp32 channels-last residual stream (B, H, W, C).
+    Layer scale is a column scale of fc2's output, x + s_b * gamma (.) (W2 g + b2): the forward reads the folded operand
+    W2' = gamma (.) W2, b2' = gamma (.) b2 (CACHE.scaled); the backward forms dW2', db2' like any Linear's gradients and derives
+    dW2 = gamma (.) dW2', db2 = gamma (.) db2', dgamma = rowsum(dW2' (.) W2) + db2' (.) b2 from them once that GEMM has run
+    (`_after_wgrads`: no extra pass over activations).  dp: None (eval) or the DropPath multipliers of the branch (`drop_path_scales`).
+    Saved per block: x (the stream itself), y fp32, h, pre-GELU and GELU output in the operand dtype, stats."""
+
+    @staticmethod
+    def forward(ctx, x, dp, eps, wd, bd, gn, bn, w1, b1, w2, b2, gamma):
+        B, H, W, C = x.shape
+        M = B * H * W
+        xc = x if x.is_contiguous() else x.contiguous()
+        y, h, st = K.dwconv7_ln_fwd(xc, wd.detach().contiguous(), bd.detach(), gn.detach(), bn.detach(), eps)
+        h2 = h.view(M, C)
+        pre = torch.empty((M, w1.shape[0]), dtype=K.adt(), device=x.device)
+        g = K.gemm_nt(h2, CACHE.mat(w1), bias=b1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
+        if gamma is None:
+            w2o, b2o = CACHE.mat(w2), b2.detach()
+        else:
+            w2o, b2o = CACHE.scaled(w2, gamma), CACHE.scaled_vec(b2, gamma)
+        out = _branch_gemm(g, w2o, b2o, xc.view(M, C), C, dp)
+        ctx.dp = dp
+        ctx.has_ls = gamma is not None
+        ctx.save_for_backward(xc, y, st, h, pre, g, wd, bd, gn, bn, w1, b1, w2, b2, *([gamma] if gamma is not None else []))
+        return out.view(B, H, W, C)
+
+    @staticmethod
+    def backward(ctx, dxo):
+        xc, y, st, h, pre, g, wd, bd, gn, bn, w1, b1, w2, b2 = ctx.saved_tensors[:14]
+        gamma = ctx.saved_tensors[14] if ctx.has_ls else None
+        B, H, W, C = xc.shape
+        M = B * H * W
+        d2 = dxo.reshape(M, C)
+        if not d2.is_contiguous():
+            d2 = d2.contiguous()
+        if d2.dtype != F32:
+            d2 = d2.float()
+        train = w1.requires_grad
+        s = ctx.dp
+        d2h = _twin(d2)
+        if d2h is None:
+            d2h = K.cast_bf16(d2)
+        if K.EXACT:
+            d2h, s = _scaled_rows(d2h, s), None
+        w2t = CACHE.mat_t(w2) if gamma is None else CACHE.scaled(w2, gamma, transposed=True)
+        dpre = _branch_dgrad(d2h, w2t, s, epilogue=K.EPI_MUL_DGELU, aux=pre)             # (M, 4C) d(pre-GELU)
+        if train:
+            if gamma is None:
+                _branch_wgrad(d2h, g, grad_buf(w2), grad_buf(b2), (w2, b2), s)
+            else:
+                # gradients of the folded layer, then the layer-scale step once they have landed (the GEMM may sit in the wgrad queue)
+                tw = torch.zeros(w2.shape, dtype=F32, device=xc.device)
+                tb = torch.zeros(b2.shape, dtype=F32, device=xc.device)
+                _branch_wgrad(d2h, g, tw, tb, (), s)
+
+                def finish(tw=tw, tb=tb, w2=w2, b2=b2, gamma=gamma):
+                    K.layer_scale_grads(tw, tb, w2.detach(), b2.detach(), gamma.detach(), grad_buf(w2) if w2.requires_grad else None,
+                                        grad_buf(b2) if b2.requires_grad else None, grad_buf(gamma) if gamma.requires_grad else None)
+                _after_wgrads(finish, (gamma, w2, b2))
+        dh = K.gemm_nt(dpre, CACHE.mat_t(w1))                                            # (M, C)
+        if train:
+            _tn(dpre, h.view(M, C), grad_buf(w1), grad_buf(b1), (w1, b1))
+        dx, dy = K.dwconv7_ln_bwd_data(dh, y, st, gn.detach(), wd.detach().contiguous(), dout=d2,
+                                       dgamma=grad_buf(gn) if train else None, dbeta=grad_buf(bn) if train else None, defer=_defer())
+        _after_deferred()
+        if train:
+            K.dwconv7_bwd_weight(dy, xc, grad_buf(wd), grad_buf(bd))
+            _tn_notify(wd, bd, gn, bn)
+        return (dx,) + (None,) * 11
+
+
+def convnext_block(x, params: Sequence[Optional[torch.Tensor]], dp=None, eps: float = 1e-6):
+    """x (B, H, W, C) fp32 channels-last -> x + drop_path(gamma * pwconv2(gelu(pwconv1(LN(dwconv(x)))))).
+    params: [dwconv.weight, dwconv.bias, norm.weight, norm.bias, pwconv1.weight, pwconv1.bias, pwconv2.weight, pwconv2.bias, gamma | None]."""
+    if x.shape[-1] % 8 != 0:
+        raise ValueError(f"ConvNeXt block: the channel count must be a multiple of 8 (got {x.shape[-1]})")
+    return ConvNeXtBlockFn.apply(x, dp, eps, *params)
+
+
+class Conv2x2S2Fn(torch.autograd.Function):
+    """2x2 stride-2 convolution without padding on a channels-last map (ConvNeXt downsample layers, reference backbone/convnext.py:111-114)
+    as a patch gather + GEMM 4C -> Cout: x (B, H, W, C) in the operand dtype -> (B, H // 2, W // 2, Cout) fp32; an odd last row / column is
+    dropped as nn.Conv2d does.  The gather is a strided copy in (ky, kx, c) column order (c innermost, whole channel rows move); the
+    weight operand is reordered once to that order and cached.  Forward, input gradient and weight gradient are the library's GEMMs."""
+
+    @staticmethod
+    def _wmat(weight, transposed):
+        def make():
+            w = weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1).contiguous()
+            return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
+        return CACHE._get(weight, "c2t" if transposed else "c2", make)
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        B, H, W, C = x.shape
+        Co = weight.shape[0]
+        Ho, Wo = H // 2, W // 2
+        x16 = x if x.dtype == K.adt() else x.to(K.adt())
+        col = x16[:, :2 * Ho, :2 * Wo].reshape(B, Ho, 2, Wo, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B * Ho * Wo, 4 * C)
+        out = K.gemm_nt(col, Conv2x2S2Fn._wmat(weight, False), bias=None if bias is None else bias.detach(), out_dtype=F32)
+        ctx.save_for_backward(col, weight, bias)
+        ctx.shape = (B, H, W, C, Ho, Wo)
+        ctx.in_dtype = x.dtype
+        return out.view(B, Ho, Wo, Co)
+
+    @staticmethod
+    def backward(ctx, dy):
+        col, weight, bias = ctx.saved_tensors
+        B, H, W, C, Ho, Wo = ctx.shape
+        Co = weight.shape[0]
+        dy2 = dy.reshape(B * Ho * Wo, Co)
+        dy2 = K.cast_bf16(dy2.float().contiguous()) if dy2.dtype != K.adt() else dy2.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dcol = K.gemm_nt(dy2, Conv2x2S2Fn._wmat(weight, True))                            # (M, 4C) in (ky, kx, c) order
+            dx6 = dcol.view(B, Ho, Wo, 2, 2, C).permute(0, 1, 3, 2, 4, 5)                     # adjoint of the gather
+            if H == 2 * Ho and W == 2 * Wo:
+                dx = dx6.reshape(B, H, W, C)
+            else:
+                dx = dcol.new_zeros((B, H, W, C))
+                dx[:, :2 * Ho, :2 * Wo] = dx6.reshape(B, 2 * Ho, 2 * Wo, C)
+            if dx.dtype != ctx.in_dtype:
+                dx = dx.to(ctx.in_dtype)
+        if weight.requires_grad:
+            dw = torch.zeros((Co, 4 * C), dtype=F32, device=dy.device)
+            db = torch.zeros((Co,), dtype=F32, device=dy.device) if bias is not None else None
+            K.gemm_tn(dy2, col, dw, db)
+            grad_buf(weight).add_(dw.view(Co, 2, 2, C).permute(0, 3, 1, 2))
+            if bias is not None:
+                grad_buf(bias).add_(db)
+            _tn_notify(weight, bias)
+        return dx, None, None
+
+
+def conv2x2_s2(x_nhwc, weight, bias=None):
+    """x (B, H, W, Cin) channels-last -> (B, H // 2, W // 2, Cout) fp32."""
+    return Conv2x2S2Fn.apply(x_nhwc, weight, bias)
