@@ -93,7 +93,9 @@ int uenc_segment_colsum(const void* x16, long ld, int cols, const int64_t* seg_s
  * y = GroupNorm(x) [+ bilinear_resize(add_src, align_corners=False)] [ReLU] for x, y (B, HW, C) fp32|bf16 (torch.nn.GroupNorm
  * semantics over (HW x C/G) per image and group).  stats (B, G, 2) = (mean, rstd) is written for the backward; scratch:
  * uenc_groupnorm_tokens_scratch_bytes().  add_src: NULL or fp32 (B, Hs, Ws, C), then HW == H * W.  C % G == 0, (C/G) % 4 == 0,
- * 64 % (C/G) == 0, 256 % (C/4) == 0. */
+ * 64 % (C/G) == 0, 256 % (C/4) == 0.  relu != 0 together with add_src != NULL returns UENC_EINVAL: the backward has no add_src
+ * argument and recomputes the ReLU mask from xhat * gamma + beta alone, without the merged term, so the pair could only be
+ * differentiated wrongly.  (The reference's ReLU follows the output convolution, never the merge.) */
 long uenc_groupnorm_tokens_scratch_bytes(int B, int HW, int C, int G);
 int uenc_groupnorm_tokens_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype,
                               float* stats, void* scratch, const float* add_src, int Hs, int Ws, int H, int W, int B, int HW,

@@ -233,7 +233,7 @@ extern "C" long uenc_groupnorm_tokens_scratch_bytes(int B, int HW, int C, int G)
 }
 
 // y = GroupNorm(x) [+ bilinear_resize(add_src)] [ReLU] on token matrices; stats (B, G, 2) = (mean, rstd) is written for
-// the backward.  add_src: optional fp32 (B, Hs, Ws, C) map (then HW == H * W).
+// the backward.  add_src: optional fp32 (B, Hs, Ws, C) map (then HW == H * W); not together with relu (UENC_EINVAL).
 extern "C" int uenc_groupnorm_tokens_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype,
                                          float* stats, void* scratch, const float* add_src, int Hs, int Ws, int H, int W, int B, int HW,
                                          int C, int G, float eps, int relu, hipStream_t stream) {
@@ -242,6 +242,9 @@ extern "C" int uenc_groupnorm_tokens_fwd(const void* x, int x_dtype, const float
     if (rc != UENC_OK) return rc;
     UENC_CHECK_ARG(y && (y_dtype == UENC_F32 || y_dtype == UENC_BF16) && ((uintptr_t)y & 7) == 0);
     UENC_CHECK_ARG(add_src == nullptr || (Hs > 0 && Ws > 0 && H > 0 && W > 0 && (long)H * W == HW));
+    // uenc_groupnorm_tokens_bwd recomputes the ReLU mask from xhat * gamma + beta alone: with a merged term in front of the
+    // ReLU that mask would be wrong, so the combination is refused here rather than differentiated wrongly there.
+    UENC_CHECK_ARG(!(relu != 0 && add_src != nullptr));
     p.y = y; p.y_f32 = (y_dtype == UENC_F32); p.eps = eps; p.relu = relu; p.add_src = add_src; p.H = H; p.W = W; p.Hs = Hs; p.Ws = Ws;
     hipLaunchKernelGGL(gn_reduce_kernel<0>, dim3(p.nchunk, B), dim3(GN_THREADS), 0, stream, p);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, stream, p);
