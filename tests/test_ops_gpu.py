@@ -739,3 +739,104 @@ def test_wgrad_store_first_equals_accumulate():
     ops.linear(xa, lin.weight, lin.bias, out_dtype=torch.float32).square().mean().backward()
     ops.flush_wgrads()
     assert relerr(lin.weight.grad, ref_single) < 1e-5                     # the 7s were overwritten: the tile was stored
+
+
+def _fused_gn_case(C, G, seed=1):
+    import torch.nn as nn
+    gn = nn.GroupNorm(G, C).cuda()
+    with torch.no_grad():
+        gn.weight.copy_(_r(C, seed=seed) * 0.3 + 1.0); gn.bias.copy_(_r(C, seed=seed + 1) * 0.3)
+    return gn
+
+
+@pytest.mark.parametrize("relu,merge", [(False, False), (True, False), (False, True)])
+def test_linear_group_norm_fn(ops, relu, merge):
+    """The fused 1x1 conv + GroupNorm (+ ReLU | + bilinear top-down merge) node against torch's ops in fp32 on the bf16-rounded
+    operands, forward and every gradient.  12 x 20 tokens per image: not a multiple of the GEMM tile (ragged M)."""
+    import torch.nn as nn
+    B, H, W, Ci, C, G = 2, 12, 20, 64, 256, 32
+    conv = nn.Conv2d(Ci, C, 1).cuda()
+    with torch.no_grad():
+        conv.weight.copy_(_r(C, Ci, 1, 1, seed=6) * Ci ** -0.5); conv.bias.copy_(_r(C, seed=7) * 0.2)
+    gn = _fused_gn_case(C, G)
+    x = _r(B, H * W, Ci, seed=3).to(torch.bfloat16).requires_grad_()
+    src = _r(B, H // 2, W // 2, C, seed=4).requires_grad_() if merge else None
+    y = ops.linear_group_norm(x, conv, gn, relu=relu, add_src=src, add_hw=(H, W) if merge else None, out_dtype=torch.float32)
+    dy = _r(B, H * W, C, seed=5)
+    y.backward(dy)
+    ops.flush_wgrads()
+    got = [y.detach(), x.grad, conv.weight.grad.clone(), conv.bias.grad.clone(), gn.weight.grad.clone(), gn.bias.grad.clone()]
+    got += [src.grad] if merge else []
+    x2 = x.detach().float().requires_grad_()
+    w2 = conv.weight.detach().to(torch.bfloat16).float().requires_grad_()
+    b2, g2, be2 = (t.detach().clone().requires_grad_() for t in (conv.bias, gn.weight, gn.bias))
+    ref = F.group_norm(F.conv2d(x2.transpose(1, 2).reshape(B, Ci, H, W), w2, b2), G, g2, be2, gn.eps)
+    if merge:
+        s2 = src.detach().clone().requires_grad_()
+        ref = ref + F.interpolate(s2.permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=False)
+    if relu:
+        ref = F.relu(ref)
+    ref = ref.flatten(2).transpose(1, 2)
+    ref.backward(dy)
+    want = [ref.detach(), x2.grad, w2.grad, b2.grad, g2.grad, be2.grad] + ([s2.grad] if merge else [])
+    for name, a, b in zip(["y", "dx", "dW", "db", "dgamma", "dbeta", "dsrc"], got, want):
+        _check(name, a, b, 1e-2 if name == "y" else 2e-2)
+    ops.CACHE.invalidate()
+
+
+def test_conv3x3_group_norm_fn(ops):
+    """The fused 3x3 conv + GroupNorm + ReLU node (the FPN's output conv) against torch's ops, as test_linear_group_norm_fn."""
+    B, H, W, Ci, C, G = 2, 12, 20, 64, 256, 32
+    gn = _fused_gn_case(C, G)
+    x = _r(B, H, W, Ci, seed=3).to(torch.bfloat16).requires_grad_()
+    w = (_r(C, Ci, 3, 3, seed=2) * (9 * Ci) ** -0.5).requires_grad_()
+    y = ops.conv3x3_group_norm(x, w, gn, relu=True, out_dtype=torch.float32)
+    dy = _r(B, H * W, C, seed=5)
+    y.backward(dy)
+    ops.flush_wgrads()
+    x2 = x.detach().float().requires_grad_()
+    w2 = w.detach().to(torch.bfloat16).float().requires_grad_()
+    g2, be2 = (t.detach().clone().requires_grad_() for t in (gn.weight, gn.bias))
+    ref = F.relu(F.group_norm(F.conv2d(x2.permute(0, 3, 1, 2), w2, padding=1), G, g2, be2, gn.eps)).flatten(2).transpose(1, 2)
+    ref.backward(dy)
+    _check("y", y, ref, 1e-2)
+    for name, a, b in [("dx", x.grad, x2.grad), ("dW", w.grad, w2.grad), ("dgamma", gn.weight.grad, g2.grad), ("dbeta", gn.bias.grad, be2.grad)]:
+        _check(name, a, b, 2e-2)
+    ops.CACHE.invalidate()
+
+
+@pytest.mark.parametrize("node", ["linear", "conv3x3"])
+def test_fused_nodes_saved_tensor_semantics(ops, node):
+    """The fused nodes keep what their inner Functions save on the autograd ctx: a retained graph runs backward twice (same dx both
+    times, bit for bit: neither node's input gradient goes through an atomic), a released one raises autograd's RuntimeError, and so
+    does an in-place write to a saved input (the token map for the Linear node; the 3x3 node saves its patch matrix, not the map
+    itself, so there it is the conv weight)."""
+    import torch.nn as nn
+    B, H, W, C, G = 1, 8, 8, 64, 8
+    gn = _fused_gn_case(C, G)
+    if node == "linear":
+        conv = nn.Conv2d(C, C, 1).cuda()
+        x = _r(B, H * W, C, seed=3).to(torch.bfloat16).requires_grad_()
+        run = lambda: ops.linear_group_norm(x, conv, gn, out_dtype=torch.float32)
+        saved = x
+    else:
+        w = (_r(C, C, 3, 3, seed=2) * (9 * C) ** -0.5).requires_grad_()
+        x = _r(B, H, W, C, seed=3).to(torch.bfloat16).requires_grad_()
+        run = lambda: ops.conv3x3_group_norm(x, w, gn, relu=True, out_dtype=torch.float32)
+        saved = w
+    dy = _r(B, H * W, C, seed=5)
+    y = run()
+    y.backward(dy, retain_graph=True)
+    g1 = x.grad.clone()
+    y.backward(dy, retain_graph=True)
+    assert torch.equal(x.grad, 2 * g1)
+    y.backward(dy)
+    with pytest.raises(RuntimeError, match="second time"):
+        y.backward(dy)
+    y = run()
+    with torch.no_grad():
+        saved.add_(1.0)
+    with pytest.raises(RuntimeError, match="inplace"):       # autograd's saved-tensor check (its wording differs for a saved view)
+        y.backward(dy)
+    ops.flush_wgrads()
+    ops.CACHE.invalidate()

@@ -6,7 +6,8 @@ in `BACKBONE_REGISTRY` with `cfg.MODEL.CONVNEXT.*` (config.add_convnext_config).
 
 The residual stream is an fp32 channels-last map (B, H, W, C), as in the DiNAT path.  A Block is one autograd Function
 (`ops.ConvNeXtBlockFn`): the fused 7x7 depthwise convolution + LayerNorm kernel (csrc/dwconv.hip), the bf16 MFMA GEMMs with GELU /
-residual / DropPath epilogues, layer scale folded into the second GEMM's operand.  The 4x4 stride-4 stem is the K = 48 patch GEMM of
+residual / DropPath epilogues, layer scale folded into the second GEMM's operand; the GELU-MLP branch (`ops._gelu_mlp_fwd` /
+`ops._gelu_mlp_bwd`) is the one the Swin / DiNAT block body runs.  The 4x4 stride-4 stem is the K = 48 patch GEMM of
 the Swin PatchEmbed, the 2x2 stride-2 downsample convolutions are a patch gather + GEMM (`ops.conv2x2_s2`); a `channels_first`
 LayerNorm of a map that is stored channels-last is the ordinary row LayerNorm.  Stochastic depth is applied in training mode, one draw
 per block and sample (`ops.drop_path_scales`).  The kernels need channel counts that are multiples of 8 (every stock width is).

@@ -7,10 +7,11 @@ parameter names and shapes (`backbone.patch_embed.proj.{0,1}`, `backbone.levels.
 
 `NeighborhoodAttention2D` stands in for `natten.NeighborhoodAttention2D` (`dinat.py:14`): the reference takes it from
 the un-vendored wheel natten==0.14.4, so its arithmetic is restated from NATTEN's published algorithm (oracle/
-dinat_ref.py, parity unpinned) and runs in `csrc/na2d.hip`.  A NATLayer is one autograd Function (`ops.NATLayerFn`):
+dinat_ref.py, parity unpinned) and runs in `csrc/na2d.hip`.  A NATLayer is one autograd Function (`ops.NATLayerFn`: the
+block body of the Swin path, `ops._block_fwd` / `ops._block_bwd`, with a neighbourhood-attention adapter in the middle):
 LayerNorm, bf16 MFMA GEMMs with bias / GELU / residual epilogues and the neighbourhood-attention kernels, on an
 fp32 channels-last residual stream; the 3x3 stride-2 convolutions of the tokenizer and the downsamplers are patch
-gathers + the same GEMMs (`ops.ConvS2Fn`).
+gathers + the same GEMMs (`ops.ConvS2Fn`, on the weight-operand and wgrad helpers every patch-gather convolution uses).
 
 Stochastic depth is applied in training mode as in the Swin path (`ops.drop_path_scales`).  Not reproduced: the
 dropout layers (rate 0 in the shipped config, config.py:235-236); `layer_scale` (never passed by `D2DiNAT`,

@@ -6,7 +6,8 @@ constructor arguments, same parameter / buffer names and shapes (so reference ch
 as a persistent buffer, ...), same `forward(x) -> {"res2".."res5"}` contract, registered as
 `D2SwinTransformer` in `BACKBONE_REGISTRY`.
 
-What differs is how a block runs: one autograd Function per block (`ops.SwinBlockFn`) launching the
+What differs is how a block runs: one autograd Function per block (`ops.SwinBlockFn`, a thin wrapper
+around the pre-norm block body `ops._block_fwd` / `ops._block_bwd` that the DiNAT path shares) launching the
 fused kernels — LayerNorm, bf16 MFMA GEMMs with bias/GELU/residual epilogues and the shifted-window
 attention kernel that folds pad / roll / partition / reverse / crop into addressing — instead of the
 reference's ~40 ATen calls and 4-6 full-tensor copies per block (swin.py:250-289).

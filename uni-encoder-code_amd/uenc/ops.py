@@ -9,6 +9,7 @@ Conventions
     on demand), the way a fused gradient-accumulation does: the Functions return None for them.  A
     data-parallel wrapper (`uenc.dp`) can point `.grad` at flat all-reduce buckets beforehand.
 """
+import copy
 import os
 import weakref
 from typing import List, Optional, Sequence, Tuple
@@ -537,10 +538,7 @@ def _tn(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: Optional[torch.
         WGRADS.add_small(dy, x, gw, gb, notify, alpha)
         return
     K.gemm_tn(dy, x, gw, gb, alpha=alpha)
-    if WGRADS.busy():
-        WGRADS.notify.extend(p for p in notify if p is not None)     # keep notification order behind the queued groups
-    else:
-        _notify(*notify)
+    _tn_notify(*notify)                                               # keep notification order behind the queued groups
 
 
 _BIG_M = 8192      # from this many rows on, an fp32 operand is first copied to bf16: the LDS-DMA GEMM kernels read bf16 only
@@ -1046,10 +1044,7 @@ def _branch_wgrad(g16, x, gw, gb, notify, scales):
         else:
             b += 1
     if not runs:
-        if WGRADS.busy():
-            WGRADS.notify.extend(p for p in notify if p is not None)
-        else:
-            _notify(*notify)
+        _tn_notify(*notify)
         return
     alpha = float(max(scales))
     for i, (b0, b1) in enumerate(runs):
@@ -1057,87 +1052,136 @@ def _branch_wgrad(g16, x, gw, gb, notify, scales):
         _tn(g16[rows], x[rows], gw, gb, notify if i == len(runs) - 1 else (), alpha=alpha)
 
 
-class SwinBlockFn(torch.autograd.Function):
-    """One whole SwinTransformerBlock (reference backbone/swin.py:235-295) as 7 kernels forward and
-    13 backward, all HIP.  x is the fp32 residual stream (B, L, C).  dp: None (eval) or (scales_attn, scales_mlp), the
-    per-sample DropPath multipliers of the two residual branches in training mode (`drop_path_scales`)."""
+def _gelu_mlp_fwd(xin, w1, b1, w2, b2, gamma, res, scales):
+    """Forward tail of a block's MLP branch: fc1 + GELU (the pre-activation is kept for the backward), then res + scale_b * fc2(.)
+    through `_branch_gemm`.  gamma: None, or ConvNeXt's layer scale, folded into fc2's operand (CACHE.scaled).  -> pre, h, out."""
+    pre = torch.empty((xin.shape[0], w1.shape[0]), dtype=K.adt(), device=xin.device)
+    h = K.gemm_nt(xin, CACHE.mat(w1), bias=b1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
+    if gamma is None:
+        w2o, b2o = CACHE.mat(w2), b2.detach()
+    else:
+        w2o, b2o = CACHE.scaled(w2, gamma), CACHE.scaled_vec(b2, gamma)
+    return pre, h, _branch_gemm(h, w2o, b2o, res, res.shape[1], scales)
 
-    @staticmethod
-    def forward(ctx, x, H, W, ws, shift, nH, scale, dp, g1, b1, wqkv, bqkv, table, wproj, bproj, g2, b2, w1, bb1, w2, bb2):
-        B, L, C = x.shape
-        s1, s2 = dp if dp is not None else (None, None)
-        M = B * L
-        x2 = x.reshape(M, C)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        xn, _, st1 = K.layernorm_fwd(x2, g1.detach(), b1.detach(), out_dtype=BF16)
-        qkv = K.gemm_nt(xn, CACHE.mat(wqkv), bias=bqkv.detach())
+
+def _gelu_mlp_bwd(dxo, scales, pre, xin, w1, b1, w2t, fc2_wgrad, train):
+    """Head of that branch's backward, from the incoming stream gradient dxo (C last) to d(fc1 input), both wgrads included.
+    -> (d2, dxin): the stream gradient as a contiguous fp32 (M, C) matrix (the skip path still needs it) and d(xin) bf16.
+    w2t: fc2's transposed operand; `fc2_wgrad(g16, scales)` accumulates fc2's gradients from the unscaled bf16 gradient (`_branch_wgrad`
+    into .grad, or ConvNeXt's folded layer-scale path) -- called between the two dgrad GEMMs, where its queue entries belong."""
+    d2 = dxo.reshape(-1, dxo.shape[-1])
+    if not d2.is_contiguous():
+        d2 = d2.contiguous()
+    if d2.dtype != F32:
+        d2 = d2.float()
+    # bf16 copy of the stream gradient (the dgrad / wgrad GEMMs read bf16 operands)
+    d2h = _twin(d2)                                     # written by the LayerNorm backward that produced this gradient
+    if d2h is None:
+        d2h = K.cast_bf16(d2)
+    if K.EXACT:
+        d2h, scales = _scaled_rows(d2h, scales), None   # (verification mode: the scaled gradient is materialised)
+    # DropPath: the branch sees scale_b * gradient -- applied in the dgrad epilogue and as the wgrad's alpha
+    dpre = _branch_dgrad(d2h, w2t, scales, epilogue=K.EPI_MUL_DGELU, aux=pre)            # (M, 4C) d(pre-GELU)
+    if train:
+        fc2_wgrad(d2h, scales)
+    dxin = K.gemm_nt(dpre, CACHE.mat_t(w1))                                              # (M, C)
+    if train:
+        _tn(dpre, xin, grad_buf(w1), grad_buf(b1), (w1, b1))
+    return d2, dxin
+
+
+def _block_fwd(ctx, x2, dp, att, params):
+    """The pre-norm block Swin and DiNAT share, 7 kernels: LN1 -> qkv -> attention -> proj (+x) -> LN2 -> fc1 + GELU -> fc2 (+x).
+    x2: the fp32 residual stream (M, C); dp: None (eval) or (scales_attn, scales_mlp), the per-sample DropPath multipliers of the
+    two residual branches in training mode (`drop_path_scales`); params: the 13 block parameters, the attention's own (position
+    table / rpb) fifth.  att, the attention adapter: `forward(qkv, bqkv, apar, needs_grad)` -> (output viewable as (M, C), extra
+    tensors to save), `backward(qkv, bqkv, apar, attn, dattn, extra, train)` -> dqkv, its own parameters' .grad written in place."""
+    g1, b1, wqkv, bqkv, apar, wproj, bproj, g2, b2, w1, bb1, w2, bb2 = params
+    s1, s2 = dp if dp is not None else (None, None)
+    M, C = x2.shape
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    xn, _, st1 = K.layernorm_fwd(x2, g1.detach(), b1.detach(), out_dtype=BF16)
+    qkv = K.gemm_nt(xn, CACHE.mat(wqkv), bias=None if bqkv is None else bqkv.detach())
+    attn, extra = att.forward(qkv, bqkv, apar, any(ctx.needs_input_grad))
+    x1 = _branch_gemm(attn.view(M, C), CACHE.mat(wproj), bproj.detach(), x2, C, s1)
+    xn2, _, st2 = K.layernorm_fwd(x1, g2.detach(), b2.detach(), out_dtype=BF16)
+    pre, h, out = _gelu_mlp_fwd(xn2, w1, bb1, w2, bb2, None, x1, s2)
+    ctx.dp, ctx.att = (s1, s2), att
+    ctx.save_for_backward(x2, st1, xn, qkv, attn, x1, st2, xn2, pre, h, *params, *extra)
+    return out
+
+
+def _block_bwd(ctx, dxo):
+    """Backward of `_block_fwd`, 13 kernels: -> dx (M, C) fp32.  Parameter gradients go straight into .grad."""
+    sv = ctx.saved_tensors
+    x2, st1, xn, qkv, attn, x1, st2, xn2, pre, h = sv[:10]
+    g1, b1, wqkv, bqkv, apar, wproj, bproj, g2, b2, w1, bb1, w2, bb2 = sv[10:23]
+    M, C = x2.shape
+    train = wqkv.requires_grad
+    s1, s2 = ctx.dp
+    # MLP branch
+    d2, dxn2 = _gelu_mlp_bwd(dxo, s2, pre, xn2, w1, bb1, CACHE.mat_t(w2),
+                             lambda g16, s: _branch_wgrad(g16, h, grad_buf(w2), grad_buf(bb2), (w2, bb2), s), train)
+    tw = []
+    dx1 = _ln_bwd(dxn2, x1, st2, g2.detach(), dres=d2,
+                  dgamma=grad_buf(g2) if train else None, dbeta=grad_buf(b2) if train else None, twin=tw)
+    # attention branch
+    dx1h = tw[0]
+    if K.EXACT:
+        dx1h, s1 = _scaled_rows(dx1h, s1), None
+    dattn = _branch_dgrad(dx1h, CACHE.mat_t(wproj), s1)                                # (M, C) bf16
+    if train:
+        _branch_wgrad(dx1h, attn.view(M, C), grad_buf(wproj), grad_buf(bproj), (wproj, bproj), s1)
+    dqkv2 = ctx.att.backward(qkv, bqkv, apar, attn, dattn, sv[23:], train).view(M, 3 * C)
+    dxn = K.gemm_nt(dqkv2, CACHE.mat_t(wqkv))
+    if train:
+        _tn(dqkv2, xn, grad_buf(wqkv), None if bqkv is None else grad_buf(bqkv), (wqkv, bqkv))
+    tw = []
+    dx = _ln_bwd(dxn, x2, st1, g1.detach(), dres=dx1,
+                 dgamma=grad_buf(g1) if train else None, dbeta=grad_buf(b1) if train else None, twin=tw)
+    _register_twin(dx, tw[0])                           # the previous block's backward starts from dx in bf16
+    if train:
+        _tn_notify(g1, b1, apar, g2, b2)
+    return dx
+
+
+class _WindowAttn:
+    """Attention adapter of the block body for Swin: fused shifted-window attention on the qkv GEMM's output."""
+
+    def __init__(self, *geom):
+        self.geom = geom                                  # (B, H, W, ws, shift, scale)
+
+    def forward(self, qkv, bqkv, table, needs_grad):
+        B, H, W, ws, shift, scale = self.geom
         bias_q = bias_k = CACHE.relpos(table, ws)         # (the kernels read bias_q only; refreshed for all blocks by one launch per step)
         # the softmax row statistics are kept for the backward of 12 x 12 windows (its kernel then skips the maximum / sum passes)
-        want_lse = ws == 12 and not K.EXACT and any(ctx.needs_input_grad)
-        attn = K.window_attn_fwd(qkv.view(B, H, W, 3 * C), CACHE.vec16(bqkv), bias_q, ws, shift, scale, want_lse=want_lse)
+        want_lse = ws == 12 and not K.EXACT and needs_grad
+        attn = K.window_attn_fwd(qkv.view(B, H, W, -1), CACHE.vec16(bqkv), bias_q, ws, shift, scale, want_lse=want_lse)
         attn, lse = attn if want_lse else (attn, None)
-        ctx.has_lse = lse is not None
-        x1 = _branch_gemm(attn.view(M, C), CACHE.mat(wproj), bproj.detach(), x2, C, s1)
-        xn2, _, st2 = K.layernorm_fwd(x1, g2.detach(), b2.detach(), out_dtype=BF16)
-        pre = torch.empty((M, w1.shape[0]), dtype=K.adt(), device=x.device)
-        h = K.gemm_nt(xn2, CACHE.mat(w1), bias=bb1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
-        x2o = _branch_gemm(h, CACHE.mat(w2), bb2.detach(), x1, C, s2)
-        ctx.dp = (s1, s2)
-        ctx.save_for_backward(x2, st1, xn, qkv, bias_q, bias_k, attn, x1, st2, xn2, pre, h,
-                              g1, b1, wqkv, bqkv, table, wproj, bproj, g2, b2, w1, bb1, w2, bb2, *([lse] if lse is not None else []))
-        ctx.geom = (B, L, C, H, W, ws, shift, nH, scale)
-        return x2o.view(B, L, C)
+        return attn, (bias_q, bias_k) + (() if lse is None else (lse,))
+
+    def backward(self, qkv, bqkv, table, attn, dattn, extra, train):
+        B, H, W, ws, shift, scale = self.geom
+        bias_q, bias_k = extra[:2]
+        # (the kernels add the relative-position-table gradient and the padding-slot share of the qkv-bias gradient straight into .grad)
+        return _wattn_bwd(qkv.view(B, H, W, -1), CACHE.vec16(bqkv), bias_q, bias_k, attn, dattn.view(B, H, W, -1), ws, shift, scale,
+                          dtable=grad_buf(table) if train else None, dbias=grad_buf(bqkv) if train else None,
+                          lse=extra[2] if len(extra) > 2 else None)
+
+
+class SwinBlockFn(torch.autograd.Function):
+    """One whole SwinTransformerBlock (reference backbone/swin.py:235-295) as 7 kernels forward and 13 backward, all HIP: the shared
+    block body (`_block_fwd` / `_block_bwd`) around window attention.  x is the fp32 residual stream (B, L, C); dp as in `_block_fwd`."""
+
+    @staticmethod
+    def forward(ctx, x, H, W, ws, shift, nH, scale, dp, *params):
+        B, L, C = x.shape
+        return _block_fwd(ctx, x.reshape(B * L, C), dp, _WindowAttn(B, H, W, ws, shift, scale), params).view(B, L, C)
 
     @staticmethod
     def backward(ctx, dxo):
-        (x2, st1, xn, qkv, bias_q, bias_k, attn, x1, st2, xn2, pre, h,
-         g1, b1, wqkv, bqkv, table, wproj, bproj, g2, b2, w1, bb1, w2, bb2) = ctx.saved_tensors[:25]
-        lse = ctx.saved_tensors[25] if ctx.has_lse else None
-        B, L, C, H, W, ws, shift, nH, scale = ctx.geom
-        M = B * L
-        d2 = dxo.reshape(M, C)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
-        train = wqkv.requires_grad
-        # MLP branch (bf16 copy of the incoming stream gradient: the dgrad / wgrad GEMMs read bf16 operands)
-        s1, s2 = ctx.dp
-        d2h = _twin(d2)                                     # written by the LayerNorm backward that produced this gradient
-        if d2h is None:
-            d2h = K.cast_bf16(d2)
-        if K.EXACT:
-            d2h, s2 = _scaled_rows(d2h, s2), None           # (verification mode: the scaled gradient is materialised)
-        # DropPath: the MLP branch sees scale_b * gradient -- applied in the dgrad epilogue and as the wgrad's alpha
-        dh = _branch_dgrad(d2h, CACHE.mat_t(w2), s2, epilogue=K.EPI_MUL_DGELU, aux=pre)     # (M, 4C) d(pre-GELU)
-        if train:
-            _branch_wgrad(d2h, h, grad_buf(w2), grad_buf(bb2), (w2, bb2), s2)
-        dxn2 = K.gemm_nt(dh, CACHE.mat_t(w1))                                              # (M, C)
-        if train:
-            _tn(dh, xn2, grad_buf(w1), grad_buf(bb1), (w1, bb1))
-        tw = []
-        dx1 = _ln_bwd(dxn2, x1, st2, g2.detach(), dres=d2,
-                              dgamma=grad_buf(g2) if train else None, dbeta=grad_buf(b2) if train else None, twin=tw)
-        # attention branch
-        dx1h = tw[0]
-        if K.EXACT:
-            dx1h, s1 = _scaled_rows(dx1h, s1), None
-        dattn = _branch_dgrad(dx1h, CACHE.mat_t(wproj), s1)                                # (M, C) bf16
-        if train:
-            _branch_wgrad(dx1h, attn.view(M, C), grad_buf(wproj), grad_buf(bproj), (wproj, bproj), s1)
-        # (the kernels add the relative-position-table gradient and the padding-slot share of the qkv-bias gradient straight into .grad)
-        dqkv = _wattn_bwd(qkv.view(B, H, W, 3 * C), CACHE.vec16(bqkv), bias_q, bias_k, attn, dattn.view(B, H, W, C), ws, shift, scale,
-                                 dtable=grad_buf(table) if train else None, dbias=grad_buf(bqkv) if train else None, lse=lse)
-        dqkv2 = dqkv.view(M, 3 * C)
-        dxn = K.gemm_nt(dqkv2, CACHE.mat_t(wqkv))
-        if train:
-            _tn(dqkv2, xn, grad_buf(wqkv), grad_buf(bqkv), (wqkv, bqkv))
-        tw = []
-        dx = _ln_bwd(dxn, x2, st1, g1.detach(), dres=dx1,
-                             dgamma=grad_buf(g1) if train else None, dbeta=grad_buf(b1) if train else None, twin=tw)
-        _register_twin(dx, tw[0])                           # the previous block's backward starts from dx in bf16
-        if train:
-            _tn_notify(g1, b1, table, g2, b2)
-        return (dx.view(B, L, C),) + (None,) * 20
+        return (_block_bwd(ctx, dxo).view(dxo.shape),) + (None,) * 20
 
 
 def swin_block(x, H, W, ws, shift, nH, scale, params: Sequence[torch.Tensor], dp=None):
@@ -1472,27 +1516,65 @@ def group_norm_tokens(x, gn, *, relu=False, add_src=None, add_hw=None, out_dtype
     return GroupNormTokensFn.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, add_src, add_hw, out_dtype, dx_dtype)
 
 
+def _conv_wmat(weight, tag, transposed=False, pad8=False):
+    """Cached GEMM operand of a patch-gather convolution: weight (Cout, Cin, kh, kw) reordered to the patch matrix's (ky, kx, c)
+    column order, (Cout, kh * kw * Cin) -- pad8: both sizes zero-padded to multiples of 8 -- or its transpose for the dgrad GEMM."""
+    def make():
+        w = weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1)
+        if pad8:
+            w = F.pad(w, (0, -w.shape[1] % 8, 0, -w.shape[0] % 8))
+        w = w.contiguous()
+        return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
+    return CACHE._get(weight, tag + "t" if transposed else tag, make)
+
+
+def _conv_dy(dy, M, Co):
+    """The incoming gradient of a patch-gather convolution as the contiguous (M, Cout) operand of its two backward GEMMs."""
+    dy2 = dy.reshape(M, Co)
+    dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
+    return dy2 if dy2.dtype == K.adt() else K.cast_bf16(dy2.float())
+
+
+def _conv_wgrad(dy2, col, weight, bias, gemm=None):
+    """Weight (+ bias) gradient of a patch-gather convolution: dy2^T col into a zeroed (Np, Kp) temp by the TN GEMM, its valid part
+    added to weight.grad through the inverse of `_conv_wmat`'s reordering, the bias slice to bias.grad, then the notification."""
+    Co, C, kh, kw = weight.shape
+    dw = torch.zeros((dy2.shape[1], col.shape[1]), dtype=F32, device=dy2.device)
+    db = torch.zeros((dy2.shape[1],), dtype=F32, device=dy2.device) if bias is not None else None
+    (gemm or K.gemm_tn)(dy2, col, dw, db)
+    grad_buf(weight).add_(dw[:Co, :kh * kw * C].view(Co, kh, kw, C).permute(0, 3, 1, 2))
+    if bias is not None:
+        grad_buf(bias).add_(db[:Co])
+    _tn_notify(weight, bias)
+
+
 class Conv3x3Fn(torch.autograd.Function):
     """The single 3x3 conv of the FPN (reference pixel_decoder/msdeformattn.py:293-302 `layer_1`, 154 GFLOP per image
     at 1/4 resolution).  x (B, H, W, Cin) bf16 channels-last; weight (Cout, Cin, 3, 3) -> (B, H*W, Cout) fp32.  Forward:
     patch matrix (B*H*W, 9*Cin) + the 256x256 LDS-DMA GEMM; backward: dgrad GEMM + col2im gather, wgrad through the
-    token-contraction GEMM on the saved patch matrix."""
+    token-contraction GEMM on the saved patch matrix (`_conv_wgrad`)."""
 
     @staticmethod
-    def _wmat(weight):
-        return CACHE._get(weight, "c3", lambda: K.cast_bf16(weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1).contiguous()))
-
-    @staticmethod
-    def _wmat_t(weight):
-        return CACHE._get(weight, "c3t", lambda: K.cast_transpose_bf16(
-            weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1).contiguous()))
+    def _wgrad_gemm(dy2, col, dw, db):
+        M, Co = dy2.shape
+        Kd = col.shape[1]
+        if M % 64 == 0 and Co % 8 == 0 and not K.EXACT:
+            tile = 256 if Co % 256 == 0 else 128
+            nsplit = max(1, M // 16384)
+            mlen = -(-(M // 64) // nsplit) * 64
+            nsplit = -(-M // mlen)
+            tiles_k = -(-Kd // tile)
+            WgradQueue.launch(tile, [(dy2.data_ptr(), col.data_ptr(), dw.data_ptr(), 0, Co, Kd, Kd, M, Co, Kd, tiles_k, mlen,
+                                      nsplit, -(-Co // tile) * tiles_k * nsplit, 0)], dy2.device)
+        else:
+            K.gemm_tn(dy2, col, dw, None)
 
     @staticmethod
     def forward(ctx, x, weight):
         B, H, W, C = x.shape
         x16 = x if x.dtype == K.adt() else x.to(K.adt())
         col = K.im2col3x3(x16 if x16.is_contiguous() else x16.contiguous())
-        out = K.gemm_nt(col, Conv3x3Fn._wmat(weight), out_dtype=F32)
+        out = K.gemm_nt(col, _conv_wmat(weight, "c3"), out_dtype=F32)
         ctx.save_for_backward(col, weight)
         ctx.shape = (B, H, W, C)
         ctx.in_dtype = x.dtype
@@ -1502,32 +1584,14 @@ class Conv3x3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         col, weight = ctx.saved_tensors
         B, H, W, C = ctx.shape
-        Co = weight.shape[0]
-        dy2 = dy.reshape(B * H * W, Co)
-        dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
-        if dy2.dtype != BF16:
-            dy2 = K.cast_bf16(dy2.float())
+        dy2 = _conv_dy(dy, B * H * W, weight.shape[0])
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = K.gemm_nt(dy2, Conv3x3Fn._wmat_t(weight))                                  # (M, 9*Cin) bf16
+            dcol = K.gemm_nt(dy2, _conv_wmat(weight, "c3", True))                             # (M, 9*Cin) bf16
             dx = K.col2im3x3(dcol, B, H, W, C)
-            if ctx.in_dtype != dx.dtype:
-                dx = dx.to(ctx.in_dtype)
+            dx = dx if dx.dtype == ctx.in_dtype else dx.to(ctx.in_dtype)
         if weight.requires_grad:
-            M = B * H * W
-            dw = torch.zeros((Co, 9 * C), dtype=F32, device=dy.device)
-            if M % 64 == 0 and Co % 8 == 0 and not K.EXACT:
-                tile = 256 if Co % 256 == 0 else 128
-                nsplit = max(1, M // 16384)
-                mlen = -(-(M // 64) // nsplit) * 64
-                nsplit = -(-M // mlen)
-                tiles_k = -(-(9 * C) // tile)
-                WgradQueue.launch(tile, [(dy2.data_ptr(), col.data_ptr(), dw.data_ptr(), 0, Co, 9 * C, 9 * C, M, Co, 9 * C, tiles_k, mlen,
-                                          nsplit, -(-Co // tile) * tiles_k * nsplit, 0)], dy.device)
-            else:
-                K.gemm_tn(dy2, col, dw, None)
-            grad_buf(weight).add_(dw.view(Co, 3, 3, C).permute(0, 3, 1, 2))
-            _tn_notify(weight)
+            _conv_wgrad(dy2, col, weight, None, Conv3x3Fn._wgrad_gemm)
         return dx, None
 
 
@@ -1537,14 +1601,35 @@ def conv3x3(x_nhwc, weight):
 
 
 class _SubCtx:
-    """The part of an autograd ctx the Functions above use, for running one Function inside another (below)."""
+    """The part of an autograd ctx the Functions above use, for running one Function inside another (below).  It keeps the inner
+    Function's non-tensor state (rows, cfg, shape ...); the tensors it saves only pass through on their way to the outer ctx."""
+    saved_tensors = ()
 
     def __init__(self, needs):
         self.needs_input_grad = tuple(needs)
-        self.saved_tensors = ()
 
     def save_for_backward(self, *tensors):
         self.saved_tensors = tensors
+
+
+def _save_inner(ctx, *subs):
+    """Register the inner Functions' saved tensors (entries may be None) on the outer ctx: autograd owns them, hooks and checks included."""
+    ctx.save_for_backward(*(t for c in subs for t in c.saved_tensors))
+    ctx.counts = tuple(len(c.saved_tensors) for c in subs)
+    for c in subs:
+        del c.saved_tensors
+    ctx.subs = subs
+
+
+def _inner(ctx):
+    """The inner ctx objects for one backward call: copies of the forward's, each with its slice of the outer saved tensors."""
+    saved, out, i = ctx.saved_tensors, [], 0
+    for c, n in zip(ctx.subs, ctx.counts):
+        c = copy.copy(c)
+        c.saved_tensors = saved[i:i + n]
+        out.append(c)
+        i += n
+    return out
 
 
 class LinearGroupNormFn(torch.autograd.Function):
@@ -1560,13 +1645,12 @@ class LinearGroupNormFn(torch.autograd.Function):
         y = LinearFn.forward(ca, x, weight, bias, None, None, F32)
         cb = _SubCtx((True, False, False, False, False, False, ctx.needs_input_grad[8], False, False, False))
         out = GroupNormTokensFn.forward(cb, y, gamma, beta, G, eps, relu, add_src, add_hw, out_dtype, BF16)
-        ctx.sub = (ca, cb)
+        _save_inner(ctx, ca, cb)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        ca, cb = ctx.sub
-        ctx.sub = None
+        ca, cb = _inner(ctx)
         g = GroupNormTokensFn.backward(cb, dy)             # g[0]: d(conv output) bf16, g[6]: d(add_src)
         dx = LinearFn.backward(ca, g[0])[0]
         return dx, None, None, None, None, None, None, None, g[6], None, None
@@ -1581,13 +1665,12 @@ class Conv3x3GroupNormFn(torch.autograd.Function):
         y = Conv3x3Fn.forward(ca, x_nhwc, weight)
         cb = _SubCtx((True, False, False, False, False, False, False, False, False, False))
         out = GroupNormTokensFn.forward(cb, y, gamma, beta, G, eps, relu, None, None, out_dtype, BF16)
-        ctx.sub = (ca, cb)
+        _save_inner(ctx, ca, cb)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        ca, cb = ctx.sub
-        ctx.sub = None
+        ca, cb = _inner(ctx)
         g = GroupNormTokensFn.backward(cb, dy)
         dx = Conv3x3Fn.backward(ca, g[0])[0]
         return dx, None, None, None, None, None, None, None
@@ -1636,80 +1719,38 @@ def na2d(qkv, rpb, nH: int, ks: int, dilation: int, scale: float):
     return NA2DFn.apply(qkv, rpb, nH, ks, dilation, scale)
 
 
+class _NeighborhoodAttn:
+    """Attention adapter of the block body (`_block_fwd`) for DiNAT: uenc_na2d on the qkv GEMM's output, H, W >= ks * dilation."""
+
+    def __init__(self, *geom):
+        self.geom = geom                                  # (B, H, W, nH, ks, dilation, scale)
+
+    def forward(self, qkv, bqkv, rpb, needs_grad):
+        B, H, W, nH, ks, dilation, scale = self.geom
+        rp = rpb.detach().float().contiguous()
+        attn, lse = K.na2d_fwd(qkv.view(B, H, W, -1), rp, nH, ks, dilation, scale)
+        return attn, (rp, lse)
+
+    def backward(self, qkv, bqkv, rpb, attn, dattn, extra, train):
+        B, H, W, nH, ks, dilation, scale = self.geom
+        rp, lse = extra
+        return K.na2d_bwd(qkv.view(B, H, W, -1), rp, attn, dattn.view(B, H, W, -1), lse, nH, ks, dilation, scale,
+                          grad_buf(rpb) if (train and rpb.requires_grad) else None)
+
+
 class NATLayerFn(torch.autograd.Function):
-    """One whole NATLayer without layer scale (reference backbone/dinat.py:90-97): LN1 -> qkv -> neighbourhood attention ->
-    proj (+x) -> LN2 -> fc1 + GELU -> fc2 (+x), the same kernel sequence as ops.SwinBlockFn with uenc_na2d in the middle.
-    x is the fp32 residual stream (B, H, W, C), H, W >= ks * dilation.  dp: as in SwinBlockFn (DropPath scales, training mode)."""
+    """One whole NATLayer without layer scale (reference backbone/dinat.py:90-97): the block body SwinBlockFn runs (`_block_fwd` /
+    `_block_bwd`) with neighbourhood attention in the middle; the qkv bias may be None.  x is the fp32 residual stream (B, H, W, C),
+    H, W >= ks * dilation.  dp: as in `_block_fwd` (DropPath scales, training mode)."""
 
     @staticmethod
-    def forward(ctx, x, nH, ks, dilation, scale, dp, g1, b1, wqkv, bqkv, rpb, wproj, bproj, g2, b2, w1, bb1, w2, bb2):
+    def forward(ctx, x, nH, ks, dilation, scale, dp, *params):
         B, H, W, C = x.shape
-        s1, s2 = dp if dp is not None else (None, None)
-        M = B * H * W
-        x2 = x.reshape(M, C)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        xn, _, st1 = K.layernorm_fwd(x2, g1.detach(), b1.detach(), out_dtype=BF16)
-        qkv = K.gemm_nt(xn, CACHE.mat(wqkv), bias=None if bqkv is None else bqkv.detach())
-        rp = rpb.detach().float().contiguous()
-        attn, lse = K.na2d_fwd(qkv.view(B, H, W, 3 * C), rp, nH, ks, dilation, scale)
-        x1 = _branch_gemm(attn.view(M, C), CACHE.mat(wproj), bproj.detach(), x2, C, s1)
-        xn2, _, st2 = K.layernorm_fwd(x1, g2.detach(), b2.detach(), out_dtype=BF16)
-        pre = torch.empty((M, w1.shape[0]), dtype=K.adt(), device=x.device)
-        h = K.gemm_nt(xn2, CACHE.mat(w1), bias=bb1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
-        x2o = _branch_gemm(h, CACHE.mat(w2), bb2.detach(), x1, C, s2)
-        ctx.dp = (s1, s2)
-        ctx.save_for_backward(x2, st1, xn, qkv, rp, lse, attn, x1, st2, xn2, pre, h,
-                              g1, b1, wqkv, bqkv, rpb, wproj, bproj, g2, b2, w1, bb1, w2, bb2)
-        ctx.geom = (B, H, W, C, nH, ks, dilation, scale)
-        return x2o.view(B, H, W, C)
+        return _block_fwd(ctx, x.reshape(B * H * W, C), dp, _NeighborhoodAttn(B, H, W, nH, ks, dilation, scale), params).view(B, H, W, C)
 
     @staticmethod
     def backward(ctx, dxo):
-        (x2, st1, xn, qkv, rp, lse, attn, x1, st2, xn2, pre, h,
-         g1, b1, wqkv, bqkv, rpb, wproj, bproj, g2, b2, w1, bb1, w2, bb2) = ctx.saved_tensors
-        B, H, W, C, nH, ks, dilation, scale = ctx.geom
-        M = B * H * W
-        d2 = dxo.reshape(M, C)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
-        if d2.dtype != F32:
-            d2 = d2.float()
-        train = wqkv.requires_grad
-        s1, s2 = ctx.dp
-        d2h = _twin(d2)
-        if d2h is None:
-            d2h = K.cast_bf16(d2)
-        if K.EXACT:
-            d2h, s2 = _scaled_rows(d2h, s2), None
-        dh = _branch_dgrad(d2h, CACHE.mat_t(w2), s2, epilogue=K.EPI_MUL_DGELU, aux=pre)
-        if train:
-            _branch_wgrad(d2h, h, grad_buf(w2), grad_buf(bb2), (w2, bb2), s2)
-        dxn2 = K.gemm_nt(dh, CACHE.mat_t(w1))
-        if train:
-            _tn(dh, xn2, grad_buf(w1), grad_buf(bb1), (w1, bb1))
-        tw = []
-        dx1 = _ln_bwd(dxn2, x1, st2, g2.detach(), dres=d2,
-                              dgamma=grad_buf(g2) if train else None, dbeta=grad_buf(b2) if train else None, twin=tw)
-        dx1h = tw[0]
-        if K.EXACT:
-            dx1h, s1 = _scaled_rows(dx1h, s1), None
-        dattn = _branch_dgrad(dx1h, CACHE.mat_t(wproj), s1)
-        if train:
-            _branch_wgrad(dx1h, attn.view(M, C), grad_buf(wproj), grad_buf(bproj), (wproj, bproj), s1)
-        dqkv = K.na2d_bwd(qkv.view(B, H, W, 3 * C), rp, attn, dattn.view(B, H, W, C), lse, nH, ks, dilation, scale,
-                          grad_buf(rpb) if (train and rpb.requires_grad) else None)
-        dqkv2 = dqkv.view(M, 3 * C)
-        dxn = K.gemm_nt(dqkv2, CACHE.mat_t(wqkv))
-        if train:
-            _tn(dqkv2, xn, grad_buf(wqkv), None if bqkv is None else grad_buf(bqkv), (wqkv, bqkv))
-        tw = []
-        dx = _ln_bwd(dxn, x2, st1, g1.detach(), dres=dx1,
-                             dgamma=grad_buf(g1) if train else None, dbeta=grad_buf(b1) if train else None, twin=tw)
-        _register_twin(dx, tw[0])
-        if train:
-            _tn_notify(g1, b1, rpb, g2, b2)
-        return (dx.view(B, H, W, C),) + (None,) * 18
+        return (_block_bwd(ctx, dxo).view(dxo.shape),) + (None,) * 18
 
 
 def nat_layer(x, nH, ks, dilation, scale, params: Sequence[torch.Tensor], dp=None):
@@ -1731,14 +1772,6 @@ class ConvS2Fn(torch.autograd.Function):
         return torch.cat(taps, dim=-1).reshape(B * Ho * Wo, Kp)
 
     @staticmethod
-    def _wmat(weight, Kp, transposed):
-        def make():
-            w = weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1)
-            w = F.pad(w, (0, Kp - w.shape[1], 0, -weight.shape[0] % 8)).contiguous()
-            return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
-        return CACHE._get(weight, "s2t" if transposed else "s2", make)
-
-    @staticmethod
     def forward(ctx, x, weight, bias):
         B, H, W, C = x.shape
         Co = weight.shape[0]
@@ -1748,7 +1781,7 @@ class ConvS2Fn(torch.autograd.Function):
         # patch matrix by the HIP gather when the channel count allows 16-byte pieces, else by strided slices (the 3-channel image)
         col = K.im2col3x3_s2(x16.contiguous()) if C % 8 == 0 else ConvS2Fn._patches(x16, Ho, Wo, Kp)
         Np = -(-Co // 8) * 8
-        out = K.gemm_nt(col, ConvS2Fn._wmat(weight, Kp, False), bias=_bias_pad(bias, Np), out_dtype=F32)
+        out = K.gemm_nt(col, _conv_wmat(weight, "s2", pad8=True), bias=_bias_pad(bias, Np), out_dtype=F32)
         ctx.save_for_backward(col, weight, bias)
         ctx.shape = (B, H, W, C, Ho, Wo, Kp, Np)
         ctx.in_dtype = x.dtype
@@ -1759,32 +1792,24 @@ class ConvS2Fn(torch.autograd.Function):
         col, weight, bias = ctx.saved_tensors
         B, H, W, C, Ho, Wo, Kp, Np = ctx.shape
         Co = weight.shape[0]
-        dy2 = dy.reshape(B * Ho * Wo, Co)
-        dy2 = K.cast_bf16(dy2.float().contiguous()) if dy2.dtype != BF16 else dy2.contiguous()
+        dy2 = _conv_dy(dy, B * Ho * Wo, Co)
         if Np != Co:
             dy2 = F.pad(dy2, (0, Np - Co))
         dx = None
         if ctx.needs_input_grad[0]:
             if C % 8 == 0:
-                dcol = K.gemm_nt(dy2, ConvS2Fn._wmat(weight, Kp, True))                          # (M, 9C) bf16
+                dcol = K.gemm_nt(dy2, _conv_wmat(weight, "s2", True, pad8=True))                          # (M, 9C) bf16
                 dx = K.col2im3x3_s2(dcol, B, H, W, C)
-                if ctx.in_dtype != F32:
-                    dx = dx.to(ctx.in_dtype)
+                dx = dx if dx.dtype == ctx.in_dtype else dx.to(ctx.in_dtype)
             else:
-                dcol = K.gemm_nt(dy2, ConvS2Fn._wmat(weight, Kp, True), out_dtype=F32).view(B, Ho, Wo, Kp)
+                dcol = K.gemm_nt(dy2, _conv_wmat(weight, "s2", True, pad8=True), out_dtype=F32).view(B, Ho, Wo, Kp)
                 dxp = dcol.new_zeros((B, 2 * Ho + 2, 2 * Wo + 2, C))
                 for t in range(9):                                        # adjoint of the strided gather
                     dyy, dxx = divmod(t, 3)
                     dxp[:, dyy:dyy + 2 * Ho:2, dxx:dxx + 2 * Wo:2, :] += dcol[..., t * C:(t + 1) * C]
                 dx = dxp[:, 1:1 + H, 1:1 + W, :].to(ctx.in_dtype)
         if weight.requires_grad:
-            dw = torch.zeros((Np, Kp), dtype=F32, device=dy.device)
-            db = torch.zeros((Np,), dtype=F32, device=dy.device) if bias is not None else None
-            K.gemm_tn(dy2, col, dw, db)
-            grad_buf(weight).add_(dw[:Co, :9 * C].view(Co, 3, 3, C).permute(0, 3, 1, 2))
-            if bias is not None:
-                grad_buf(bias).add_(db[:Co])
-            _tn_notify(weight, bias)
+            _conv_wgrad(dy2, col, weight, bias)
         return dx, None, None
 
 
@@ -1837,14 +1862,7 @@ class ConvNeXtBlockFn(torch.autograd.Function):
         M = B * H * W
         xc = x if x.is_contiguous() else x.contiguous()
         y, h, st = K.dwconv7_ln_fwd(xc, wd.detach().contiguous(), bd.detach(), gn.detach(), bn.detach(), eps)
-        h2 = h.view(M, C)
-        pre = torch.empty((M, w1.shape[0]), dtype=K.adt(), device=x.device)
-        g = K.gemm_nt(h2, CACHE.mat(w1), bias=b1.detach(), epilogue=K.EPI_GELU, aux_out=pre)
-        if gamma is None:
-            w2o, b2o = CACHE.mat(w2), b2.detach()
-        else:
-            w2o, b2o = CACHE.scaled(w2, gamma), CACHE.scaled_vec(b2, gamma)
-        out = _branch_gemm(g, w2o, b2o, xc.view(M, C), C, dp)
+        pre, g, out = _gelu_mlp_fwd(h.view(M, C), w1, b1, w2, b2, gamma, xc.view(M, C), dp)
         ctx.dp = dp
         ctx.has_ls = gamma is not None
         ctx.save_for_backward(xc, y, st, h, pre, g, wd, bd, gn, bn, w1, b1, w2, b2, *([gamma] if gamma is not None else []))
@@ -1855,37 +1873,23 @@ class ConvNeXtBlockFn(torch.autograd.Function):
         xc, y, st, h, pre, g, wd, bd, gn, bn, w1, b1, w2, b2 = ctx.saved_tensors[:14]
         gamma = ctx.saved_tensors[14] if ctx.has_ls else None
         B, H, W, C = xc.shape
-        M = B * H * W
-        d2 = dxo.reshape(M, C)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
-        if d2.dtype != F32:
-            d2 = d2.float()
         train = w1.requires_grad
-        s = ctx.dp
-        d2h = _twin(d2)
-        if d2h is None:
-            d2h = K.cast_bf16(d2)
-        if K.EXACT:
-            d2h, s = _scaled_rows(d2h, s), None
-        w2t = CACHE.mat_t(w2) if gamma is None else CACHE.scaled(w2, gamma, transposed=True)
-        dpre = _branch_dgrad(d2h, w2t, s, epilogue=K.EPI_MUL_DGELU, aux=pre)             # (M, 4C) d(pre-GELU)
-        if train:
+
+        def fc2_wgrad(d2h, s):
             if gamma is None:
                 _branch_wgrad(d2h, g, grad_buf(w2), grad_buf(b2), (w2, b2), s)
-            else:
-                # gradients of the folded layer, then the layer-scale step once they have landed (the GEMM may sit in the wgrad queue)
-                tw = torch.zeros(w2.shape, dtype=F32, device=xc.device)
-                tb = torch.zeros(b2.shape, dtype=F32, device=xc.device)
-                _branch_wgrad(d2h, g, tw, tb, (), s)
+                return
+            # gradients of the folded layer, then the layer-scale step once they have landed (the GEMM may sit in the wgrad queue)
+            tw = torch.zeros(w2.shape, dtype=F32, device=xc.device)
+            tb = torch.zeros(b2.shape, dtype=F32, device=xc.device)
+            _branch_wgrad(d2h, g, tw, tb, (), s)
 
-                def finish(tw=tw, tb=tb, w2=w2, b2=b2, gamma=gamma):
-                    K.layer_scale_grads(tw, tb, w2.detach(), b2.detach(), gamma.detach(), grad_buf(w2) if w2.requires_grad else None,
-                                        grad_buf(b2) if b2.requires_grad else None, grad_buf(gamma) if gamma.requires_grad else None)
-                _after_wgrads(finish, (gamma, w2, b2))
-        dh = K.gemm_nt(dpre, CACHE.mat_t(w1))                                            # (M, C)
-        if train:
-            _tn(dpre, h.view(M, C), grad_buf(w1), grad_buf(b1), (w1, b1))
+            def finish():
+                K.layer_scale_grads(tw, tb, w2.detach(), b2.detach(), gamma.detach(), grad_buf(w2) if w2.requires_grad else None,
+                                    grad_buf(b2) if b2.requires_grad else None, grad_buf(gamma) if gamma.requires_grad else None)
+            _after_wgrads(finish, (gamma, w2, b2))
+        w2t = CACHE.mat_t(w2) if gamma is None else CACHE.scaled(w2, gamma, transposed=True)
+        d2, dh = _gelu_mlp_bwd(dxo, ctx.dp, pre, h.view(B * H * W, C), w1, b1, w2t, fc2_wgrad, train)
         dx, dy = K.dwconv7_ln_bwd_data(dh, y, st, gn.detach(), wd.detach().contiguous(), dout=d2,
                                        dgamma=grad_buf(gn) if train else None, dbeta=grad_buf(bn) if train else None, defer=_defer())
         _after_deferred()
@@ -1910,20 +1914,13 @@ class Conv2x2S2Fn(torch.autograd.Function):
     weight operand is reordered once to that order and cached.  Forward, input gradient and weight gradient are the library's GEMMs."""
 
     @staticmethod
-    def _wmat(weight, transposed):
-        def make():
-            w = weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1).contiguous()
-            return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
-        return CACHE._get(weight, "c2t" if transposed else "c2", make)
-
-    @staticmethod
     def forward(ctx, x, weight, bias):
         B, H, W, C = x.shape
         Co = weight.shape[0]
         Ho, Wo = H // 2, W // 2
         x16 = x if x.dtype == K.adt() else x.to(K.adt())
         col = x16[:, :2 * Ho, :2 * Wo].reshape(B, Ho, 2, Wo, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B * Ho * Wo, 4 * C)
-        out = K.gemm_nt(col, Conv2x2S2Fn._wmat(weight, False), bias=None if bias is None else bias.detach(), out_dtype=F32)
+        out = K.gemm_nt(col, _conv_wmat(weight, "c2"), bias=None if bias is None else bias.detach(), out_dtype=F32)
         ctx.save_for_backward(col, weight, bias)
         ctx.shape = (B, H, W, C, Ho, Wo)
         ctx.in_dtype = x.dtype
@@ -1934,27 +1931,19 @@ class Conv2x2S2Fn(torch.autograd.Function):
         col, weight, bias = ctx.saved_tensors
         B, H, W, C, Ho, Wo = ctx.shape
         Co = weight.shape[0]
-        dy2 = dy.reshape(B * Ho * Wo, Co)
-        dy2 = K.cast_bf16(dy2.float().contiguous()) if dy2.dtype != K.adt() else dy2.contiguous()
+        dy2 = _conv_dy(dy, B * Ho * Wo, Co)
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = K.gemm_nt(dy2, Conv2x2S2Fn._wmat(weight, True))                            # (M, 4C) in (ky, kx, c) order
+            dcol = K.gemm_nt(dy2, _conv_wmat(weight, "c2", True))                            # (M, 4C) in (ky, kx, c) order
             dx6 = dcol.view(B, Ho, Wo, 2, 2, C).permute(0, 1, 3, 2, 4, 5)                     # adjoint of the gather
             if H == 2 * Ho and W == 2 * Wo:
                 dx = dx6.reshape(B, H, W, C)
             else:
                 dx = dcol.new_zeros((B, H, W, C))
                 dx[:, :2 * Ho, :2 * Wo] = dx6.reshape(B, 2 * Ho, 2 * Wo, C)
-            if dx.dtype != ctx.in_dtype:
-                dx = dx.to(ctx.in_dtype)
+            dx = dx if dx.dtype == ctx.in_dtype else dx.to(ctx.in_dtype)
         if weight.requires_grad:
-            dw = torch.zeros((Co, 4 * C), dtype=F32, device=dy.device)
-            db = torch.zeros((Co,), dtype=F32, device=dy.device) if bias is not None else None
-            K.gemm_tn(dy2, col, dw, db)
-            grad_buf(weight).add_(dw.view(Co, 2, 2, C).permute(0, 3, 1, 2))
-            if bias is not None:
-                grad_buf(bias).add_(db)
-            _tn_notify(weight, bias)
+            _conv_wgrad(dy2, col, weight, bias)
         return dx, None, None
 
 
