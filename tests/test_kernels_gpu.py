@@ -665,6 +665,60 @@ def test_msdeform_fused_bwd_tiled_equals_one_kernel(K, shapes_l, spread, tile, m
         assert float((d1.float() - d0.float()).norm() / d0.float().norm()) < 2e-3
 
 
+@pytest.mark.parametrize("variant", ["7", "1", "2"])
+@pytest.mark.parametrize("shapes_l,tile", [([(9, 5)], "4,4,1"), ([(4, 8), (8, 16), (16, 32)], None)])
+def test_msdeform_ignores_retired_variant_knob(K, shapes_l, tile, variant, monkeypatch):
+    """UENC_MSDA_VARIANT used to switch phases of the shipped tiled and binned kernels off and so handed back uninitialised outputs: bit
+    flags in the tiled kernel (7: no staging, stop after staging, write nothing), an enum in the binned backward (1: drop every record,
+    2: return before the gather -- 7 never reached that kernel, so 1 and 2 are run as well).  The knob is gone: with it set, the tiled
+    forward, the fused tiled forward, the fused backward in both forms and the plain binned backward return what they return with it unset
+    -- bit for bit wherever no float atomics are involved (forward outputs, d(offaw) -- the one-kernel form stores it from registers too --,
+    grad_loc, grad_attn), grad_value within the float-atomics order.  One level with a 1 KB LDS budget (shrunk boxes, samples falling back
+    to the global gather) and three levels."""
+    if tile is not None:
+        monkeypatch.setenv("UENC_MSDA_TILE", tile)
+        monkeypatch.setenv("UENC_MSDA_TILE_BWD", tile)
+    L, P, M, D, B = len(shapes_l), 4, 8, 32, 2
+    S = sum(h * w for h, w in shapes_l)
+    gen = torch.Generator().manual_seed(31)
+    ref1 = torch.cat([torch.stack(torch.meshgrid((torch.arange(h) + 0.5) / h, (torch.arange(w) + 0.5) / w, indexing="ij"), -1).reshape(-1, 2).flip(-1)
+                      for h, w in shapes_l])
+    ref = ref1[None, :, None, :].expand(1, S, L, 2).contiguous().cuda()
+    ncol = 3 * M * L * P
+    offaw = torch.zeros(B * S, ncol)
+    offaw[:, : 2 * M * L * P] = (torch.rand(B * S, 2 * M * L * P, generator=gen) * 2 - 1) * 3.0
+    offaw[:, 2 * M * L * P:] = torch.randn(B * S, M * L * P, generator=gen) * 2
+    offaw = offaw.cuda()
+    value = torch.randn(B, S, M, D, generator=gen).to(torch.bfloat16).cuda()
+    go = torch.randn(B, S, M * D, generator=gen).to(torch.bfloat16).cuda()
+    shapes = torch.tensor(shapes_l, dtype=torch.int64).cuda()
+    start = torch.cat([shapes.new_zeros(1), (shapes[:, 0] * shapes[:, 1]).cumsum(0)[:-1]])
+    loc, aw = K.msda_prep_fwd(offaw, ref, shapes, B, S, M, L, P)
+    assert K.msdeform_fused_tiled_eligible(value, offaw, shapes_l, S, L, P)
+
+    def run():
+        exact = [K.msdeform_attn_fwd(value, shapes, start, loc, aw, out_dtype=torch.bfloat16, shapes_host=shapes_l),
+                 K.msdeform_attn_fused_fwd(value, shapes, start, offaw, ref, L, P, out_dtype=torch.bfloat16, shapes_host=shapes_l)]
+        gvs = []
+        for tiled_bwd in ("1", "0"):
+            monkeypatch.setenv("UENC_MSDA_TILED_BWD", tiled_bwd)
+            gv, d = K.msdeform_attn_fused_bwd(value, shapes, start, offaw, ref, L, P, go, shapes_l)
+            gvs.append(gv); exact.append(d)
+        gv, gl, ga = K.msdeform_attn_bwd(value, shapes, start, loc, aw, go, shapes_host=shapes_l)
+        gvs.append(gv); exact += [gl, ga]
+        return exact, gvs
+
+    monkeypatch.delenv("UENC_MSDA_VARIANT", raising=False)
+    exact0, gvs0 = run()
+    monkeypatch.setenv("UENC_MSDA_VARIANT", variant)
+    exact1, gvs1 = run()
+    for i, (t0, t1) in enumerate(zip(exact0, exact1)):
+        assert torch.equal(t0, t1), i
+    for gv0, gv1 in zip(gvs0, gvs1):
+        assert float(gv0.abs().max()) > 0
+        _close(gv1, gv0, 2e-5 * float(gv0.abs().max()) + 1e-6, 1e-4)
+
+
 @pytest.mark.parametrize("M,N,K_", [(20000, 256, 256), (86016, 256, 1024), (50000, 192, 192), (70001, 256, 2048), (33000, 200, 320)])
 def test_gemm_nt_ln_fused_epilogue(K, M, N, K_):
     """Linear -> residual add -> LayerNorm with the LayerNorm inside the GEMM epilogue (uenc_gemm_nt_ln) against uenc_gemm_nt +

@@ -1,7 +1,6 @@
 """MSDeformAttn backward timing on the pixel-decoder encoder shape of the 1024x2048 bench (GPU box).
 
-Offsets follow the reference's grid initialisation (direction per head, 1..P pixels); UENC_MSDA_VARIANT selects
-timing-only experiments compiled into the tiled kernel."""
+Offsets follow the reference's grid initialisation (direction per head, 1..P pixels)."""
 import math, os, sys, torch
 sys.path.insert(0, '/root/repo/uni-encoder-code_amd')
 from uenc import kernels as K

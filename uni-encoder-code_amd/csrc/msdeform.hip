@@ -132,7 +132,7 @@ struct MsdaTile {
     int RH, RW;                 // the map the regions are cut from: the FINEST level (the pixel decoder lists its levels coarse to fine)
     int TY, TX, ntx, nregions;  // region size on that map, regions per row / per image
     int lds_bytes;              // budget for the value tiles
-    int variant;                // timing experiments (UENC_MSDA_VARIANT): 1 = no staging, 2 = stop after staging; 0 in production
+    // (no phase-timing switches: a kernel that can skip a pass on request can return garbage; to time a phase, patch a `return` into a scratch copy)
 };
 
 __device__ __forceinline__ void msdt_fma8(const u32x4& a, const u32x4& b, const u32x4& c, const u32x4& d, float w1, float w2, float w3, float w4, float* acc) {
@@ -175,7 +175,6 @@ __global__ __launch_bounds__(MODE == 1 ? 256 : 384, MODE == 1 ? 2 : 3) void msda
     const int m = slot % p.M, unit = (slot / p.M) * 8 + xcd;
     const int b = unit / g.nregions, region = unit - b * g.nregions;
     if (b >= p.B) return;
-    if (g.variant & 4) return;
     const int ry = region / g.ntx, rx = region - ry * g.ntx;
     const int LP = p.L * p.P;
     // this region's rectangle of queries on every level: [ceil(t0 * H_l / RH), ceil(t1 * H_l / RH)) partitions level l exactly
@@ -224,7 +223,6 @@ __global__ __launch_bounds__(MODE == 1 ? 256 : 384, MODE == 1 ? 2 : 3) void msda
 #pragma unroll
         for (int l = 0; l < MSDT_L; ++l) { bx[l][0] = 0x7fffffff; bx[l][1] = -1; bx[l][2] = 0x7fffffff; bx[l][3] = -1; }
         for (int idx = tid; idx < nq; idx += nth) {
-            if (g.variant & 8) break;
             const long row1 = (long)b * p.Lq + query_of(idx);
             const float* loc = FUSED_IN ? nullptr : p.loc + (row1 * p.M + m) * LP * 2;
 #pragma unroll
@@ -308,26 +306,23 @@ __global__ __launch_bounds__(MODE == 1 ? 256 : 384, MODE == 1 ? 2 : 3) void msda
     // one L2 round trip per 6 KB).  The DMA writes lane-linearly (wave base + 16 * lane): a wave takes 16 pixels x 4 chunks of one box row,
     // and the slot swizzle is applied to the SOURCE chunk each lane fetches.
     typedef __attribute__((address_space(3))) void lds_void;
-    if (!(g.variant & 1)) {
 #pragma unroll
-        for (int l = 0; l < MSDT_L; ++l) {
-            if (loff[l] < 0) continue;
-            const bf16* lv = vbase + ((long)g.start[l] + (long)by0[l] * g.W[l] + bx0[l]) * vstride;
-            const int rowchunks = bw[l] * 4;
-            for (int row = wave; row < bh[l]; row += nwave)
-                for (int j0 = 0; j0 < rowchunks; j0 += 64) {
-                    const int j = j0 + lane;
-                    if (j < rowchunks) {
-                        const int px = j >> 2, pix = row * bw[l] + px, c = (j & 3) ^ ((pix >> 2) & 3);
-                        __builtin_amdgcn_global_load_lds(lv + ((long)row * g.W[l] + px) * vstride + c * 8,
-                                                         (lds_void*)(vt + loff[l] + (row * rowchunks + j0) * 16), 16, 0, 0);
-                    }
+    for (int l = 0; l < MSDT_L; ++l) {
+        if (loff[l] < 0) continue;
+        const bf16* lv = vbase + ((long)g.start[l] + (long)by0[l] * g.W[l] + bx0[l]) * vstride;
+        const int rowchunks = bw[l] * 4;
+        for (int row = wave; row < bh[l]; row += nwave)
+            for (int j0 = 0; j0 < rowchunks; j0 += 64) {
+                const int j = j0 + lane;
+                if (j < rowchunks) {
+                    const int px = j >> 2, pix = row * bw[l] + px, c = (j & 3) ^ ((pix >> 2) & 3);
+                    __builtin_amdgcn_global_load_lds(lv + ((long)row * g.W[l] + px) * vstride + c * 8,
+                                                     (lds_void*)(vt + loff[l] + (row * rowchunks + j0) * 16), 16, 0, 0);
                 }
-        }
-        __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0): this wave's pieces have landed
+            }
     }
+    __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0): this wave's pieces have landed
     __syncthreads();
-    if (g.variant & 2) return;
     if (BWD) {
         // pass 2 (backward): d(offaw) of every (query, head) of the region
         for (int idx = tid; idx < nq; idx += nth) {
@@ -663,7 +658,6 @@ struct MsdaBins {
     long roff[MSDA_TL];                                  // first record slot of the level within a (image, head)
     long rtot;                                           // record slots per (image, head)
     int nblk, nwork;                                     // bins / pass-B work items per (image, head)
-    int variant;                                         // timing experiments only (UENC_MSDA_VARIANT), 0 in production
     int append_only;                                     // 1: d(loc) / d(attn) come from the LDS-tiled kernel; this one writes records (and adds what overflows)
     int* count;                                          // [B * M * nblk] x MSDA_CNT_STRIDE ints (zeroed by the launcher)
     int2* rec_hd;                                        // [B * M][rtot]
@@ -731,7 +725,7 @@ __global__ __launch_bounds__(256) void msda_bwd_bin_kernel(MsdaP p, MsdaBins bn)
         const int s = j8 + round * 8;
 #pragma unroll
         for (int tp = 0; tp < 4; ++tp) code[round][tp] = 0u;
-        if (live && s < LP && bn.variant != 1) {
+        if (live && s < LP) {
             const int l = s / p.P;
             const int Hl = (int)p.shapes[2 * l], Wl = (int)p.shapes[2 * l + 1];
             MsdaTap t;
@@ -797,7 +791,7 @@ __global__ __launch_bounds__(256) void msda_bwd_bin_kernel(MsdaP p, MsdaBins bn)
         }
     }
     const bool any_ovf = __ballot(ovfbits != 0u) != 0ull;       // wave-uniform: the shuffles below are skipped when nothing overflowed
-    if (!live || bn.variant == 2) return;
+    if (!live) return;
     const bool gather = bn.append_only == 0;
     if (!gather && !any_ovf) return;
 
@@ -1037,6 +1031,36 @@ static int msda_plan_bins(const int64_t* shapes_host, int L, int Lq, int P, int 
     return 1;
 }
 
+// Scratch of a plan: one counter line per bin, then 24 bytes (rec_w 16 + rec_hd 8) per record slot.
+static long msda_workspace_bytes(const MsdaBins& bn, int B, int M) { return (long)B * M * bn.nblk * MSDA_CNT_STRIDE * 4 + (long)B * M * bn.rtot * 24; }
+
+// planned = false: no binned plan for the shape (or no shapes_host / workspace), nothing was touched; else the workgroups of passes A and B
+struct BinLaunch { bool planned; unsigned bin_grid, reduce_grid; };
+
+// The host half of the binned backward, shared by both entry points: plans the bins, checks the levels against S, the workspace and the
+// grid limits, carves count / rec_w / rec_hd out of the workspace and zeroes the counters (the first thing put on the stream).
+static int msda_bins_setup(MsdaBins& bn, const int64_t* shapes_host, void* workspace, long workspace_bytes, int B, int S, int M, int D, int L,
+                           int Lq, int P, hipStream_t stream, BinLaunch& bl) {
+    bl.planned = shapes_host != nullptr && workspace != nullptr && msda_plan_bins(shapes_host, L, Lq, P, D, bn);
+    if (!bl.planned) return UENC_OK;
+    long tot = 0;
+    for (int l = 0; l < L; ++l) tot += shapes_host[2 * l] * shapes_host[2 * l + 1];
+    const long nbins = (long)B * M * bn.nblk, cnt_bytes = nbins * MSDA_CNT_STRIDE * 4;
+    const long nchunk = (Lq + 31) / 32, nitems = (long)B * M * bn.nwork;
+    UENC_CHECK_ARG(tot == S && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= msda_workspace_bytes(bn, B, M));
+    UENC_CHECK_ARG(nbins < (1L << 31) && nchunk * B * M < (1L << 31) && (nitems + 3) / 4 < (1L << 31));
+    bn.count = (int*)workspace;
+    bn.rec_w = (float4*)((char*)workspace + cnt_bytes);                     // 16-byte records first (alignment)
+    bn.rec_hd = (int2*)((char*)workspace + cnt_bytes + (long)B * M * bn.rtot * 16);
+    bl.bin_grid = (unsigned)(nchunk * B * M); bl.reduce_grid = (unsigned)((nitems + 3) / 4);
+    return (int)msda_zero_counts(bn.count, cnt_bytes, stream);
+}
+
+static void launch_bin_reduce(const MsdaP& p, const MsdaBins& bn, unsigned grid, hipStream_t stream) {
+    if (p.go_f32) hipLaunchKernelGGL(msda_bin_reduce_kernel<true>, dim3(grid), dim3(256), 0, stream, p, bn);
+    else hipLaunchKernelGGL(msda_bin_reduce_kernel<false>, dim3(grid), dim3(256), 0, stream, p, bn);
+}
+
 static int msda_fill(MsdaP& p, const void* value, int v_dtype, const int64_t* shapes, const int64_t* level_start,
                      const float* loc, const float* attn, int B, int S, int M, int D, int L, int Lq, int P) {
     if (!(value && shapes && level_start && loc && attn)) return UENC_EINVAL;
@@ -1068,6 +1092,12 @@ extern "C" int uenc_msdeform_attn_fwd(const void* value, int v_dtype, const int6
     UENC_LAUNCH_RET();
 }
 
+// The encoder's geometry, which every LDS-tiled kernel needs: the queries are the pixels of the L level-major maps (msda_tile_setup checks
+// that the levels add up to S), 32 bf16 channels per head, and sizes the kernels' 32-bit indices and grid decoding hold.
+static bool msda_tiled_geometry_ok(int v_dtype, int B, int S, int M, int D, int L, int Lq) {
+    return D == 32 && v_dtype == UENC_BF16 && Lq == S && L <= MSDT_L && (long)B * M < 65536 && (long)B * S * M < (1L << 31) / 64;
+}
+
 // Region grid of the LDS-tiled kernels: levels from the host copy of `shapes`, regions cut from the finest map.
 static int msda_tile_setup(MsdaTile& g, const int64_t* shapes_host, int B, int S, int M, int L, bool bwd, unsigned& grid, int& threads) {
     long start = 0;
@@ -1096,7 +1126,6 @@ static int msda_tile_setup(MsdaTile& g, const int64_t* shapes_host, int B, int S
         lds_max = kb * 1024;
     }
     g.TY = ty; g.TX = tx; g.lds_bytes = kb * 1024;
-    { const char* e = getenv("UENC_MSDA_VARIANT"); g.variant = e ? atoi(e) : 0; }
     g.RH = g.H[0]; g.RW = g.W[0];
     for (int l = 1; l < L; ++l)
         if ((long)g.H[l] * g.W[l] > (long)g.RH * g.RW) { g.RH = g.H[l]; g.RW = g.W[l]; }
@@ -1123,7 +1152,7 @@ extern "C" int uenc_msdeform_attn_fwd_tiled(const void* value, int v_dtype, cons
     MsdaP p;
     int rc = msda_fill(p, value, v_dtype, shapes, level_start, loc, attn, B, S, M, D, L, Lq, P);
     if (rc != UENC_OK) return rc;
-    UENC_CHECK_ARG(out && shapes_host && D == 32 && v_dtype == UENC_BF16 && Lq == S && L <= MSDT_L && L * P <= 16 && (long)B * M < 65536 && (long)B * S * M < (1L << 31) / 64);
+    UENC_CHECK_ARG(out && shapes_host && msda_tiled_geometry_ok(v_dtype, B, S, M, D, L, Lq) && L * P <= 16);
     UENC_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)loc & 7) == 0);
     p.out = out; p.out_f32 = (out_dtype == UENC_F32);
     MsdaTile g;
@@ -1141,8 +1170,7 @@ extern "C" int uenc_msdeform_attn_fwd_tiled(const void* value, int v_dtype, cons
 extern "C" long uenc_msdeform_attn_bwd_workspace_bytes(const int64_t* shapes_host, int B, int M, int D, int L, int Lq, int P) {
     MsdaBins bn;
     if (!shapes_host || B <= 0 || M <= 0 || !msda_plan_bins(shapes_host, L, Lq, P, D, bn)) return 0;
-    const long nbins = (long)B * M * bn.nblk;
-    return nbins * MSDA_CNT_STRIDE * 4 + (long)B * M * bn.rtot * 24;
+    return msda_workspace_bytes(bn, B, M);
 }
 
 // Mirrors ms_deform_attn_backward(...): grad_value must be zero-filled by the caller (it is accumulated);
@@ -1160,26 +1188,12 @@ extern "C" int uenc_msdeform_attn_bwd(const void* value, int v_dtype, const int6
     UENC_CHECK_ARG(((uintptr_t)grad_out & 15) == 0);
     p.grad_out = grad_out; p.go_f32 = (go_dtype == UENC_F32);
     p.grad_value = grad_value; p.grad_loc = grad_loc; p.grad_attn = grad_attn;
-    MsdaBins bn;
-    if (shapes_host != nullptr && workspace != nullptr && msda_plan_bins(shapes_host, L, Lq, P, D, bn)) {
-        { const char* e = getenv("UENC_MSDA_VARIANT"); bn.variant = e ? atoi(e) : 0; }
-        long tot = 0;
-        for (int l = 0; l < L; ++l) tot += shapes_host[2 * l] * shapes_host[2 * l + 1];
-        const long nbins = (long)B * M * bn.nblk;
-        const long cnt_bytes = nbins * MSDA_CNT_STRIDE * 4;
-        const long nchunk = (Lq + 31) / 32;
-        UENC_CHECK_ARG(tot == S && ((uintptr_t)workspace & 15) == 0 &&
-                       workspace_bytes >= cnt_bytes + (long)B * M * bn.rtot * 24);
-        const long nitems = (long)B * M * bn.nwork;
-        UENC_CHECK_ARG(nbins < (1L << 31) && nchunk * B * M < (1L << 31) && (nitems + 3) / 4 < (1L << 31));
-        bn.count = (int*)workspace;
-        bn.rec_w = (float4*)((char*)workspace + cnt_bytes);                     // 16-byte records first (alignment)
-        bn.rec_hd = (int2*)((char*)workspace + cnt_bytes + (long)B * M * bn.rtot * 16);
-        hipError_t e = msda_zero_counts(bn.count, cnt_bytes, stream);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, dim3((unsigned)(nchunk * B * M)), dim3(256), 0, stream, p, bn);
-        if (p.go_f32) hipLaunchKernelGGL(msda_bin_reduce_kernel<true>, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, stream, p, bn);
-        else hipLaunchKernelGGL(msda_bin_reduce_kernel<false>, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, stream, p, bn);
+    MsdaBins bn; BinLaunch bl;
+    rc = msda_bins_setup(bn, shapes_host, workspace, workspace_bytes, B, S, M, D, L, Lq, P, stream, bl);
+    if (rc != UENC_OK) return rc;
+    if (bl.planned) {
+        hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, dim3(bl.bin_grid), dim3(256), 0, stream, p, bn);
+        launch_bin_reduce(p, bn, bl.reduce_grid, stream);
         UENC_LAUNCH_RET();
     }
     const long threads = (long)B * Lq * M * D;
@@ -1189,7 +1203,6 @@ extern "C" int uenc_msdeform_attn_bwd(const void* value, int v_dtype, const int6
     else hipLaunchKernelGGL(msda_bwd_kernel<16>, dim3(grid), dim3(256), 0, stream, p);
     UENC_LAUNCH_RET();
 }
-
 
 // ---- fused form: the sampling locations and attention weights never exist in memory ------------------------------------------
 // What ops/modules/ms_deform_attn.py:99-125 does between its two projection Linears and the native op, inside the op: the row
@@ -1231,8 +1244,7 @@ extern "C" int uenc_msdeform_attn_fused_fwd_tiled(const void* value, int v_dtype
     MsdaP p;
     int rc = msda_fill_fused(p, value, v_dtype, shapes, level_start, offaw, ld, ref, ref_per_image, B, S, M, D, L, Lq, P);
     if (rc != UENC_OK) return rc;
-    UENC_CHECK_ARG(out && shapes_host && D == 32 && v_dtype == UENC_BF16 && Lq == S && L <= MSDT_L && P == 4 && (long)B * M < 65536 &&
-                   (long)B * S * M < (1L << 31) / 64);
+    UENC_CHECK_ARG(out && shapes_host && msda_tiled_geometry_ok(v_dtype, B, S, M, D, L, Lq) && P == 4);
     UENC_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)offaw & 15) == 0 && ld % 4 == 0 && ((uintptr_t)ref & 7) == 0);
     p.out = out; p.out_f32 = (out_dtype == UENC_F32);
     MsdaTile g;
@@ -1253,34 +1265,21 @@ extern "C" int uenc_msdeform_attn_fused_bwd(const void* value, int v_dtype, cons
     UENC_CHECK_ARG(grad_out && grad_value && doffaw && shapes_host && workspace);
     UENC_CHECK_ARG(((uintptr_t)grad_out & 15) == 0 && ((uintptr_t)doffaw & 3) == 0 && ld_doffaw >= (long)3 * M * L * P && ld_doffaw % 2 == 0);
     p.grad_out = grad_out; p.go_f32 = (go_dtype == UENC_F32); p.grad_value = grad_value; p.doffaw = (bf16*)doffaw; p.ldd = ld_doffaw;
-    MsdaBins bn;
-    if (!msda_plan_bins(shapes_host, L, Lq, P, D, bn)) return UENC_EINVAL;
-    { const char* e = getenv("UENC_MSDA_VARIANT"); bn.variant = e ? atoi(e) : 0; }
-    long tot = 0;
-    for (int l = 0; l < L; ++l) tot += shapes_host[2 * l] * shapes_host[2 * l + 1];
-    const long nbins = (long)B * M * bn.nblk;
-    const long cnt_bytes = nbins * MSDA_CNT_STRIDE * 4;
-    const long nchunk = (Lq + 31) / 32;
-    UENC_CHECK_ARG(tot == S && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= cnt_bytes + (long)B * M * bn.rtot * 24);
-    const long nitems = (long)B * M * bn.nwork;
-    UENC_CHECK_ARG(nbins < (1L << 31) && nchunk * B * M < (1L << 31) && (nitems + 3) / 4 < (1L << 31));
-    bn.count = (int*)workspace;
-    bn.rec_w = (float4*)((char*)workspace + cnt_bytes);
-    bn.rec_hd = (int2*)((char*)workspace + cnt_bytes + (long)B * M * bn.rtot * 16);
-    hipError_t e = msda_zero_counts(bn.count, cnt_bytes, stream);
-    if (e != hipSuccess) return (int)e;
+    MsdaBins bn; BinLaunch bl;
+    rc = msda_bins_setup(bn, shapes_host, workspace, workspace_bytes, B, S, M, D, L, Lq, P, stream, bl);
+    if (rc != UENC_OK) return rc;
+    if (!bl.planned) return UENC_EINVAL;
     // encoder geometry (queries = the maps' pixels, P == 4, 16-byte aligned rows): d(offaw) from the LDS-tiled kernel, the binned kernel only
-    // appends its records.  UENC_MSDA_TILED_BWD=0: the one-kernel form (A/B).
-    bool tiled = Lq == S && P == 4 && L <= MSDT_L && v_dtype == UENC_BF16 && (long)B * M < 65536 && (long)B * S * M < (1L << 31) / 64 &&
+    // appends its records; the launch order pass A, tiled kernel, pass B is load-bearing (do not reorder).  UENC_MSDA_TILED_BWD=0: the one-kernel form (A/B).
+    bool tiled = msda_tiled_geometry_ok(v_dtype, B, S, M, D, L, Lq) && P == 4 &&
                  ((uintptr_t)offaw & 15) == 0 && ld % 4 == 0 && ((uintptr_t)doffaw & 15) == 0 && ld_doffaw % 8 == 0 && ((uintptr_t)ref & 7) == 0;
     { const char* ev = getenv("UENC_MSDA_TILED_BWD"); if (ev && atoi(ev) == 0) tiled = false; }
     MsdaTile g;
     unsigned tgrid = 0; int tthreads = 0;
     if (tiled && msda_tile_setup(g, shapes_host, B, S, M, L, true, tgrid, tthreads) != UENC_OK) tiled = false;
     bn.append_only = tiled ? 1 : 0;
-    hipLaunchKernelGGL(msda_bwd_bin_kernel<true>, dim3((unsigned)(nchunk * B * M)), dim3(256), 0, stream, p, bn);
+    hipLaunchKernelGGL(msda_bwd_bin_kernel<true>, dim3(bl.bin_grid), dim3(256), 0, stream, p, bn);
     if (tiled) hipLaunchKernelGGL((msda_tiled_kernel<true, 1>), dim3(tgrid), dim3(tthreads), g.lds_bytes, stream, p, g);
-    if (p.go_f32) hipLaunchKernelGGL(msda_bin_reduce_kernel<true>, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, stream, p, bn);
-    else hipLaunchKernelGGL(msda_bin_reduce_kernel<false>, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, stream, p, bn);
+    launch_bin_reduce(p, bn, bl.reduce_grid, stream);
     UENC_LAUNCH_RET();
 }

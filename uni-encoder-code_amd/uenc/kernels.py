@@ -4,6 +4,7 @@ Every wrapper validates what the kernel's grid assumes (device, dtype, inner str
 handing raw pointers to the library; the library re-checks alignment and sizes and refuses
 (-1) rather than launching on a bad shape.
 """
+import ctypes
 import os
 from typing import Optional
 
@@ -719,6 +720,19 @@ def msdeform_tiled_eligible(value, shapes_host, Lq: int, L: int, P: int) -> bool
             and sum(int(h) * int(w) for h, w in shapes_host) == S)
 
 
+def msdeform_fused_tiled_eligible(value, offaw, shapes_host, Lq: int, L: int, P: int) -> bool:
+    """The LDS-tiled FUSED forward applies: the encoder's geometry, P == 4 and 16-byte aligned projection rows.  The one place that decides
+    it: msdeform_attn_fused_fwd launches by it and DeformEncoderLayerFn chooses its forward by it."""
+    return P == 4 and offaw.stride(0) % 4 == 0 and offaw.data_ptr() % 16 == 0 and msdeform_tiled_eligible(value, shapes_host, Lq, L, P)
+
+
+def _shapes_c(shapes_host, L: int):
+    """[(H, W), ...] -> the int64[2 L] array the C entry points take as `shapes_host`."""
+    flat = [int(v) for hw in shapes_host for v in hw]
+    assert len(flat) == 2 * L
+    return (ctypes.c_int64 * len(flat))(*flat)
+
+
 def msdeform_attn_fwd(value, shapes, level_start, loc, attn, out_dtype=torch.float32, shapes_host=None):
     """value (B,S,M,D) fp32|bf16, shapes (L,2) int64, level_start (L) int64, loc (B,Lq,M,L,P,2), attn (B,Lq,M,L,P)
     -> (B, Lq, M*D).  Same tensor contract as the reference's ms_deform_attn_forward.  shapes_host: optional [(H, W), ...] host copy
@@ -732,22 +746,14 @@ def msdeform_attn_fwd(value, shapes, level_start, loc, attn, out_dtype=torch.flo
     assert loc.dtype == torch.float32 and attn.dtype == torch.float32 and attn.shape == (B, Lq, M, L, P)
     out = torch.empty((B, Lq, M * D), dtype=_odt(out_dtype), device=value.device)
     if msdeform_tiled_eligible(value, shapes_host, Lq, L, P):
-        import ctypes
-        flat = [int(v) for hw in shapes_host for v in hw]
-        sh = (ctypes.c_int64 * len(flat))(*flat)
         check(lib.uenc_msdeform_attn_fwd_tiled(value.data_ptr(), dt(value), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(),
-                                               attn.data_ptr(), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, sh, stream_ptr()),
+                                               attn.data_ptr(), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, _shapes_c(shapes_host, L), stream_ptr()),
               "msdeform_attn_fwd_tiled")
         return out
     check(lib.uenc_msdeform_attn_fwd(value.data_ptr(), dt(value), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(),
                                      attn.data_ptr(), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, stream_ptr()),
           "msdeform_attn_fwd")
     return out
-
-
-def _msda_workspace(nbytes: int, device) -> torch.Tensor:
-    """Scratch for the binned backward (bin counters + records)."""
-    return _scratch("msda_bins", nbytes, device)
 
 
 def msdeform_attn_bwd(value, shapes, level_start, loc, attn, grad_out, shapes_host=None):
@@ -762,13 +768,9 @@ def msdeform_attn_bwd(value, shapes, level_start, loc, attn, grad_out, shapes_ho
     ga = torch.empty_like(attn)
     sh, ws, ws_bytes = None, None, 0
     if shapes_host is not None:
-        import ctypes
-        flat = [int(v) for hw in shapes_host for v in hw]
-        assert len(flat) == 2 * L
-        sh = (ctypes.c_int64 * len(flat))(*flat)
-        ws_bytes = int(lib.uenc_msdeform_attn_bwd_workspace_bytes(sh, B, M, D, L, Lq, P))
+        sh, ws_bytes = _msda_host_plan(shapes_host, B, M, D, L, Lq, P)
         if ws_bytes > 0:
-            ws = _msda_workspace(ws_bytes, value.device)
+            ws = _scratch("msda_bins", ws_bytes, value.device)
     check(lib.uenc_msdeform_attn_bwd(value.data_ptr(), dt(value), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(),
                                      attn.data_ptr(), grad_out.data_ptr(), dt(grad_out), gv.data_ptr(), gl.data_ptr(),
                                      ga.data_ptr(), B, S, M, D, L, Lq, P, sh, ws.data_ptr() if ws is not None else None,
@@ -777,10 +779,8 @@ def msdeform_attn_bwd(value, shapes, level_start, loc, attn, grad_out, shapes_ho
 
 
 def _msda_host_plan(shapes_host, B, M, D, L, Lq, P):
-    import ctypes
-    flat = [int(v) for hw in shapes_host for v in hw]
-    assert len(flat) == 2 * L
-    sh = (ctypes.c_int64 * len(flat))(*flat)
+    """-> (shapes_host for C, bytes of scratch the binned backward needs: bin counters + records; 0 = no binned plan for the shape)."""
+    sh = _shapes_c(shapes_host, L)
     return sh, int(lib.uenc_msdeform_attn_bwd_workspace_bytes(sh, B, M, D, L, Lq, P))
 
 
@@ -797,13 +797,10 @@ def msdeform_attn_fused_fwd(value, shapes, level_start, offaw, ref, L: int, P: i
     Lq = ref.shape[1]
     assert offaw.dtype == torch.float32 and offaw.stride(1) == 1 and offaw.shape[0] == B * Lq and ref.dtype == torch.float32 and ref.is_contiguous()
     out = torch.empty((B, Lq, M * D), dtype=_odt(out_dtype), device=value.device)
-    if (P == 4 and offaw.stride(0) % 4 == 0 and offaw.data_ptr() % 16 == 0 and msdeform_tiled_eligible(value, shapes_host, Lq, L, P)):
-        import ctypes
-        flat = [int(v) for hw in shapes_host for v in hw]
-        sh = (ctypes.c_int64 * len(flat))(*flat)
+    if msdeform_fused_tiled_eligible(value, offaw, shapes_host, Lq, L, P):
         check(lib.uenc_msdeform_attn_fused_fwd_tiled(value.data_ptr(), dt(value), shapes.data_ptr(), level_start.data_ptr(), offaw.data_ptr(), offaw.stride(0),
-                                                     ref.data_ptr(), int(ref.shape[0] != 1), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, sh, stream_ptr()),
-              "msdeform_attn_fused_fwd_tiled")
+                                                     ref.data_ptr(), int(ref.shape[0] != 1), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, _shapes_c(shapes_host, L),
+                                                     stream_ptr()), "msdeform_attn_fused_fwd_tiled")
         return out
     check(lib.uenc_msdeform_attn_fused_fwd(value.data_ptr(), dt(value), shapes.data_ptr(), level_start.data_ptr(), offaw.data_ptr(), offaw.stride(0),
                                            ref.data_ptr(), int(ref.shape[0] != 1), out.data_ptr(), dt(out), B, S, M, D, L, Lq, P, stream_ptr()),
@@ -818,7 +815,7 @@ def msdeform_attn_fused_bwd(value, shapes, level_start, offaw, ref, L: int, P: i
     assert grad_out.is_contiguous() and grad_out.shape == (B, Lq, M * D)
     sh, ws_bytes = _msda_host_plan(shapes_host, B, M, D, L, Lq, P)
     assert ws_bytes > 0
-    ws = _msda_workspace(ws_bytes, value.device)
+    ws = _scratch("msda_bins", ws_bytes, value.device)
     gv = torch.zeros((B, S, M, D), dtype=torch.float32, device=value.device)
     ncol = 3 * M * L * P
     doffaw = torch.empty((B * Lq, ncol), dtype=torch.bfloat16, device=value.device)

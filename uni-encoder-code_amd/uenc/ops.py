@@ -1224,8 +1224,7 @@ class DeformEncoderLayerFn(torch.autograd.Function):
         # (the general gather kernel keeps the glue kernel + core pair in the forward -- its fused form measured 5 % slower, tools/msda_fused_bench.py;
         # the backward recomputes locations / weights from the saved projection row)
         v4 = value.view(B, S, nH, D)
-        if (fused and nP == 4 and offaw.stride(0) % 4 == 0 and K.msdeform_tiled_eligible(v4, shapes_host, S, L, nP)
-                and os.environ.get("UENC_MSDA_FUSED_FWD", "1") != "0"):
+        if fused and K.msdeform_fused_tiled_eligible(v4, offaw, shapes_host, S, L, nP) and os.environ.get("UENC_MSDA_FUSED_FWD", "1") != "0":
             # the queries are the maps' own pixels: the LDS-tiled kernel derives locations / weights itself (no glue kernel, no loc / aw tensors)
             att = K.msdeform_attn_fused_fwd(v4, shapes, level_start, offaw, ref, L, nP, out_dtype=BF16, shapes_host=shapes_host).view(M, C)
             loc, aw = offaw, ref
