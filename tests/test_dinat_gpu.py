@@ -34,7 +34,10 @@ def _rand(*shape, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("B,H,W,nH,ks,d", [(2, 20, 70, 2, 7, 1), (1, 33, 45, 3, 7, 2), (1, 16, 130, 1, 3, 4), (2, 13, 64, 2, 13, 1),
-                                            (1, 29, 31, 2, 5, 3), (1, 7, 7, 1, 7, 1), (1, 48, 200, 2, 7, 6)])
+                                            (1, 29, 31, 2, 5, 3), (1, 7, 7, 1, 7, 1), (1, 48, 200, 2, 7, 6),
+                                            # the VALU kernels (K >= 9): <9> with residue classes of 10 / 9 x 19 / 18 positions (the shortest = K),
+                                            # two ragged tiles per axis; <11> with two tile rows and four tile columns, the last a tail
+                                            (1, 19, 37, 1, 9, 2), (1, 12, 50, 2, 11, 1)])
 def test_na2d_kernels_vs_oracle(U, B, H, W, nH, ks, d):
     """Forward output, log-sum-exp and all four gradients (dq, dk, dv, drpb) on maps with borders on every side, ragged residue
     classes (H, W not multiples of the dilation), tail lanes (W not a multiple of 64) and the minimum size H = W = ks * d."""
@@ -66,6 +69,46 @@ def test_na2d_kernels_vs_oracle(U, B, H, W, nH, ks, d):
     # accumulation semantics of drpb
     K.na2d_bwd(qkv16.cuda(), rpb.cuda(), out, dout16.cuda(), lse, nH, ks, d, scale, drpb)
     assert rel(drpb, 2 * r.grad) < 2e-2
+
+
+def test_na2d_ignores_retired_switches(U, monkeypatch):
+    """UENC_NA2D_VARIANT (bits 1, 2, 4 used to select the direct, the LDS-tiled VALU and the prefetching dk / dv kernels) and
+    UENC_NA2D_NT (used to override the MFMA kernels' tiles per workgroup; the planner gives nt = 1 at this size, so 3 would change
+    the grid) are no longer read: with either set, out, lse and dqkv (no atomics) are bit-identical to the run without them.
+    drpb is summed with float atomics: within the oracle bound of test_na2d_kernels_vs_oracle, and within 1e-4 of the unset run
+    relative to its largest entry (the bound test_window_attention_bwd_kernel_forms_agree puts on its atomically summed gradients)."""
+    from oracle import dinat_ref as D
+    from uenc import kernels as K
+    B, H, W, nH, ks, d = 1, 33, 45, 3, 7, 2
+    C, scale = nH * 32, 32 ** -0.5
+    qkv16 = _rand(B, H, W, 3 * C, seed=1).to(torch.bfloat16)
+    rpb = _rand(nH, 2 * ks - 1, 2 * ks - 1, seed=2, scale=0.5)
+    dout16 = _rand(B, H, W, C, seed=3).to(torch.bfloat16)
+    x = qkv16.float().reshape(B, H, W, 3, nH, 32).permute(3, 0, 4, 1, 2, 5).contiguous()
+    r = rpb.clone().requires_grad_()
+    D.na2d(x[0] * scale, x[1], x[2], r, ks, d).permute(0, 2, 3, 1, 4).reshape(B, H, W, C).backward(dout16.float())
+    qkv, rpb_d, dout = qkv16.cuda(), rpb.cuda(), dout16.cuda()
+
+    def run():
+        out, lse = K.na2d_fwd(qkv, rpb_d, nH, ks, d, scale)
+        drpb = torch.zeros_like(rpb_d)
+        dqkv = K.na2d_bwd(qkv, rpb_d, out, dout, lse, nH, ks, d, scale, drpb)
+        return out, lse, dqkv, drpb
+
+    monkeypatch.delenv("UENC_NA2D_VARIANT", raising=False)
+    monkeypatch.delenv("UENC_NA2D_NT", raising=False)
+    base = run()
+    assert rel(base[3], r.grad) < 2e-2
+    for name, value in (("UENC_NA2D_VARIANT", "1"), ("UENC_NA2D_VARIANT", "2"), ("UENC_NA2D_VARIANT", "4"), ("UENC_NA2D_NT", "3")):
+        with monkeypatch.context() as mp:
+            mp.setenv(name, value)
+            got = run()
+        for what, a, b in zip(("out", "lse", "dqkv"), got, base):
+            assert torch.equal(a, b), (name, value, what)
+        spread = float((got[3] - base[3]).abs().max() / base[3].abs().max())
+        print(f"{name}={value}: drpb rel {rel(got[3], r.grad):.3e}, against the unset run {spread:.3e}")
+        assert rel(got[3], r.grad) < 2e-2, (name, value)
+        assert spread < 1e-4, (name, value, spread)
 
 
 def test_na2d_rejects_maps_smaller_than_the_window(U):

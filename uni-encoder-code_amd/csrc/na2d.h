@@ -1,4 +1,5 @@
-// Shared between na2d.hip (VALU kernels, launch entry points) and na2d_mfma.hip (MFMA kernels for window sizes <= 7).
+// Shared between na2d.hip (launch entry points; VALU kernels: window sizes >= 9, and <= 7 on maps past the MFMA kernels' 32-bit
+// index range) and na2d_mfma.hip (MFMA kernels: window sizes <= 7 -- na2d_mfma_supported is the routing predicate).
 #pragma once
 #include "common.h"
 
@@ -7,7 +8,7 @@ struct Na2d {
     const bf16* dout; bf16* dqkv; float* drpb; float* delta;
     int B, H, W, nH, d;
     float scale;
-    int hh_max, hw_max;      // bwd_kv tiled: LDS halo extents (class positions) for this launch
+    int hh_max, hw_max;      // MFMA bwd_kv: LDS halo extents (class positions) for this launch
     int tiles_x, tiles_y, nt; float inv_tiles_x;     // MFMA kernels: tiles per residue class, tiles per workgroup
 };
 
@@ -33,4 +34,4 @@ static int na2d_check(const Na2d& p, int K) {
 // na2d_mfma.hip
 int na2d_mfma_fwd(const Na2d& p, int K, hipStream_t stream);
 int na2d_mfma_bwd(Na2d& p, int K, hipStream_t stream);
-bool na2d_mfma_supported(int H, int W, int nH, int K, int dilation);
+bool na2d_mfma_supported(int H, int W, int nH, int K);

@@ -14,7 +14,8 @@
 // arithmetic of tile t and written to LDS after it, so the L2 -> LDS staging (half of every 128-byte line belongs to the neighbouring
 // head: the staging runs at the L2's line rate) overlaps the VALU-bound softmax instead of alternating with it, the bias table is
 // built once per workgroup, and the grid shrinks from one workgroup per tile (the dispatcher alone took 25 us at 12 288 tiles) to
-// a few per CU.  All index arithmetic is 32-bit (the launcher checks H * W * 3C < 2^31; integer multiplies are quarter rate).
+// a few per CU (forward and per-query backward; the per-key backward walks tiles the same way but stages each halo in place).
+// All index arithmetic is 32-bit (na2d_mfma_supported routes maps with H * W * 3C >= 2^31 to na2d.hip; integer multiplies are quarter rate).
 //
 // Bias: rpb[key - query + K - 1] per axis.  The 4 scores a lane holds per block are 4 consecutive bias columns: the table sits in LDS
 // in 4 copies shifted by 0..3 floats, so that every lane reads its 4 values with one aligned ds_read_b128.
@@ -446,9 +447,7 @@ __global__ __launch_bounds__(512) void na2d_mfma_bwd_q_kernel(Na2d p) {
 #define KV_ST 48
 #define KV_ROWS(K) (2 * (K) - 1 + 2 * KV_PR)
 
-#define NM_KV_PF_NIT 3       // prefetching form: halo positions + 32 <= 3 * 128
-
-template <int K, bool PF>
+template <int K>
 __global__ __launch_bounds__(512) void na2d_mfma_bwd_kv_kernel(Na2d p) {
     constexpr int RB = 2 * K - 1;
     const int HWQ = p.hw_max, NPOS = p.hh_max * p.hw_max + 32;
@@ -476,10 +475,7 @@ __global__ __launch_bounds__(512) void na2d_mfma_bwd_kv_kernel(Na2d p) {
     const float inv_hwq = 1.0f / (float)HWQ;
     const int c = threadIdx.x & 3;
     // staging: q and dout chunks and (chunk-0 lanes) the statistics of halo position (tid >> 2) + 128 it; zero outside the halo.
-    // PF: the loads of tile t + 1 are issued before the arithmetic of tile t and committed to LDS after it (3 passes in registers).
-    constexpr int NIT = PF ? NM_KV_PF_NIT : 1;
-    u32x4 sq[NIT], sg[NIT];
-    float2 sst[NIT];
+    // Not prefetched across tiles: holding the next halo in registers took 153 VGPRs (one workgroup per CU) and measured slower.
     auto load_pos = [&](const NmTile& t, unsigned pix0, int pos, u32x4& vq, u32x4& vg, float2& st) {
         const int yy = fdiv(pos, inv_hwq), xx = pos - yy * HWQ;
         vq = (u32x4){0u, 0u, 0u, 0u}; vg = vq; st = (float2){0.f, 0.f};
@@ -500,27 +496,19 @@ __global__ __launch_bounds__(512) void na2d_mfma_bwd_kv_kernel(Na2d p) {
             if (c == 0) ld[pos] = st;
         }
     };
-    auto issue = [&](const NmTile& t) {
-        const unsigned pix0 = (unsigned)(t.hsy * p.d + t.ry) * p.W + t.hsx * p.d + t.rx;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) load_pos(t, pix0, (threadIdx.x >> 2) + it * 128, sq[it], sg[it], sst[it]);
-    };
+    u32x4 sq, sg;
+    float2 sst;
     NmTile g = nm_tile_kv<K>(p, w, w.t0);
-    if (PF) issue(g);
     for (int t = w.t0; t < w.t1; ++t) {
         __syncthreads();                                       // the previous tile's LDS reads are done
-        if (PF) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) store_pos((threadIdx.x >> 2) + it * 128, sq[it], sg[it], sst[it]);
-        } else {
+        {
             const unsigned pix0 = (unsigned)(g.hsy * p.d + g.ry) * p.W + g.hsx * p.d + g.rx;
             for (int pos = threadIdx.x >> 2; pos < NPOS; pos += 128) {
-                load_pos(g, pix0, pos, sq[0], sg[0], sst[0]);
-                store_pos(pos, sq[0], sg[0], sst[0]);
+                load_pos(g, pix0, pos, sq, sg, sst);
+                store_pos(pos, sq, sg, sst);
             }
         }
         __syncthreads();
-        // this tile's own global operands before the prefetch (loads return in order)
         const int kyr = g.py0 + 2 * wy + (fr >> 3), kxr = g.px0 + 8 * wx + (fr & 7);
         const bool kvalid = kyr < g.Ly && kxr < g.Lx;
         const int ky = clampi(kyr, 0, g.Ly - 1), kx = clampi(kxr, 0, g.Lx - 1);
@@ -528,7 +516,7 @@ __global__ __launch_bounds__(512) void na2d_mfma_bwd_kv_kernel(Na2d p) {
         const bf16x8 kf = *(const bf16x8*)(qkv_b + pix * (unsigned)(3 * C) + C + 8 * fg);
         const bf16x8 vf = *(const bf16x8*)(qkv_b + pix * (unsigned)(3 * C) + 2 * C + 8 * fg);
         NmTile gn = g;
-        if (t + 1 < w.t1) { gn = nm_tile_kv<K>(p, w, t + 1); if (PF) issue(gn); }
+        if (t + 1 < w.t1) gn = nm_tile_kv<K>(p, w, t + 1);      // (scalar work while kf / vf are in flight)
         if (g.ok && g.py0 + 2 * wy < g.Ly && g.px0 + 8 * wx < g.Lx) {          // whole waves
             // a query attends this lane's key iff it lies in the key's inverse neighbourhood (exact, per axis)
             const int qys_k = inv_start<K>(ky), qyn_k = inv_end<K>(ky, g.Ly) - qys_k;
@@ -602,8 +590,6 @@ static dim3 nm_plan(Na2d& p) {
     int nt = (int)(total / 1536);
     nt = nt < 1 ? 1 : (nt > 8 ? 8 : nt);
     if (nt > per_class) nt = per_class;
-    const char* ev = getenv("UENC_NA2D_NT");
-    if (ev && atoi(ev) > 0) nt = atoi(ev);
     p.nt = nt;
     return dim3((per_class + nt - 1) / nt, p.d * p.d, p.B * p.nH);
 }
@@ -640,33 +626,21 @@ static void nm_kv_extents(Na2d& p, int K) {
     p.hw_max = nm_axis_extent(p.W, p.d, K, NM_TW);
 }
 
-bool na2d_mfma_supported(int H, int W, int nH, int K, int dilation) {
-    if (K > 7 || (long)H * W * 3 * nH * 32 >= (1L << 31)) return false;
-    Na2d p = {};
-    p.H = H; p.W = W; p.d = dilation;
-    nm_kv_extents(p, K);
-    return true;
-}
-
-template <int K, bool PF>
-static int nm_launch_kv2(Na2d& p, const dim3& grid, int shm, hipStream_t stream) {
-    static int attr = 0;
-    if (attr < shm) {
-        const hipError_t e = hipFuncSetAttribute((const void*)na2d_mfma_bwd_kv_kernel<K, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-        if (e != hipSuccess) return (int)e;
-        attr = shm;
-    }
-    hipLaunchKernelGGL((na2d_mfma_bwd_kv_kernel<K, PF>), grid, dim3(512), shm, stream, p);
-    return UENC_OK;
-}
+// the kernels index one image's qkv in 32 bits
+bool na2d_mfma_supported(int H, int W, int nH, int K) { return K <= 7 && (long)H * W * 3 * nH * 32 < (1L << 31); }
 
 template <int K>
 static int nm_launch_kv(Na2d& p, const dim3& grid, hipStream_t stream) {
     const int npos = p.hh_max * p.hw_max + 32;
     const int shm = npos * (64 + 64 + 8) + KV_ROWS(K) * KV_ST * 4;
-    const char* ev = getenv("UENC_NA2D_VARIANT");
-    const bool pf = npos <= NM_KV_PF_NIT * 128 && p.nt > 1 && ev && (atoi(ev) & 4);      // A/B only: the prefetching form needs 153 VGPRs (one workgroup per CU) and measured slower
-    return pf ? nm_launch_kv2<K, true>(p, grid, shm, stream) : nm_launch_kv2<K, false>(p, grid, shm, stream);
+    static int attr = 0;
+    if (attr < shm) {
+        const hipError_t e = hipFuncSetAttribute((const void*)na2d_mfma_bwd_kv_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
+        if (e != hipSuccess) return (int)e;
+        attr = shm;
+    }
+    hipLaunchKernelGGL(na2d_mfma_bwd_kv_kernel<K>, grid, dim3(512), shm, stream, p);
+    return UENC_OK;
 }
 
 template <int K>
