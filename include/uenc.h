@@ -520,6 +520,40 @@ int uenc_dwconv7_bwd_weight(const float* dy, const float* x, float* dw, float* d
 int uenc_layer_scale_grads(const float* dw2p, const float* db2p, const float* w2, const float* b2, const float* gamma, float* gw2, float* gb2,
                            float* ggamma, int N, int K, uenc_stream_t stream);
 
+/* ---- ResNet backbone (csrc/resnet.hip): stem patch gather, max pooling, BatchNorm + residual + ReLU ----------------------
+ * All maps channels-last, C % 8 == 0, 16-byte aligned; every dtype argument is UENC_F32 or UENC_BF16.  No atomics: per-channel
+ * reductions store one partial per row slab to `workspace` (uenc_bn_workspace_floats(M, C) floats) and a second launch adds the
+ * slabs in a fixed order, so the same inputs give the same bits.  Nothing is read back to the host.
+ *
+ * Patch matrix of a 7x7 stride-2 padding-3 convolution on x (B, 3, H, W) fp32 NCHW: col (B * Ho * Wo, 152), Ho = (H - 1) / 2 + 1,
+ * column (ky * 7 + kx) * 3 + c, columns 147..151 zero.  Any H, W >= 1. */
+int uenc_stem7x7_s2_patches(const float* x, void* col, int col_dtype, int B, int H, int W, uenc_stream_t stream);
+/* max_pool2d(x, 3, 2, 1) on x (B, H, W, C) -> y (B, Ho, Wo, C) of the same dtype; padding counts as -inf.  idx (B, Ho, Wo, C) bytes:
+ * the selected tap ky * 3 + kx, the first maximum in scan order (ATen's choice on ties).  The backward is a gather: every dx
+ * element (all written) adds the dy of the at most 4 windows whose idx names it, in fp32. */
+int uenc_maxpool3x3_s2_fwd(const void* x, void* y, void* idx, int dtype, int B, int H, int W, int C, uenc_stream_t stream);
+int uenc_maxpool3x3_s2_bwd(const void* dy, const void* idx, void* dx, int dtype, int B, int H, int W, int C, uenc_stream_t stream);
+long uenc_bn_workspace_floats(long M, int C);
+/* mean, var (C) fp32 = per-channel mean and biased variance over the M > 1 rows of x (M, C): Welford per thread, Chan merges across
+ * threads and slabs.  The second launch also updates running_mean / running_var (either may be NULL) with `momentum` and the
+ * unbiased variance, and adds 1 to num_batches_tracked[0] (int64, may be NULL). */
+int uenc_bn_stats(const void* x, int x_dtype, long M, int C, float* mean, float* var, float* running_mean, float* running_var,
+                  long long* num_batches_tracked, float momentum, float* workspace, long workspace_floats, uenc_stream_t stream);
+/* y = act(x * s[c] + t[c] (+ res)),  s = gamma / sqrt(var + eps),  t = beta - mean * s;  act = ReLU (relu != 0) or identity.
+ * mean / var are the batch statistics (train) or the running ones (eval, frozen); gamma / beta NULL = 1 / 0; res NULL = none. */
+int uenc_bn_act_fwd(const void* x, int x_dtype, const float* mean, const float* var, const float* gamma, const float* beta, const void* res,
+                    int res_dtype, void* y, int y_dtype, long M, int C, float eps, int relu, uenc_stream_t stream);
+/* With g = dy masked by y > 0 (relu != 0; y is the saved output) and xhat = (x - mean) / sqrt(var + eps):
+ * reduce: sums (2, C) = (sum g, sum g * xhat) over the rows; dbeta += sums[0], dgamma += sums[1] where not NULL.
+ * apply:  dx = gamma / sqrt(var + eps) * (g - sums[0] / M - xhat * sums[1] / M) (train != 0) or g * gamma / sqrt(var + eps) (eval,
+ *         frozen: x and sums unused);  dres (may be NULL) = g, the gradient of the residual branch. */
+int uenc_bn_act_bwd_reduce(const void* dy, int dy_dtype, const void* y, int y_dtype, const void* x, int x_dtype, const float* mean,
+                           const float* var, long M, int C, float eps, int relu, float* sums, float* dgamma, float* dbeta, float* workspace,
+                           long workspace_floats, uenc_stream_t stream);
+int uenc_bn_act_bwd_apply(const void* dy, int dy_dtype, const void* y, int y_dtype, const void* x, int x_dtype, const float* mean,
+                          const float* var, const float* gamma, const float* sums, void* dx, int dx_dtype, void* dres, int dres_dtype, long M,
+                          int C, float eps, int relu, int train, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

@@ -21,5 +21,6 @@ _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
 _sys.modules[__name__ + ".modeling.backbone"] = modeling.backbone
 _sys.modules[__name__ + ".modeling.backbone.convnext"] = modeling.backbone.convnext
+_sys.modules[__name__ + ".modeling.backbone.resnet"] = modeling.backbone.resnet
 
 __all__ = list(_cfg_all) + ["OneFormer", "modeling", "InstanceSegEvaluator"]

@@ -122,6 +122,15 @@ _SIGNATURES = {
     "uenc_dwconv7_bwd_weight_workspace_bytes": [c_i, c_i, c_i, c_i],
     "uenc_dwconv7_bwd_weight": [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p],
     "uenc_layer_scale_grads": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
+    # ResNet backbone: stem patch gather, max pooling, BatchNorm + residual + ReLU (csrc/resnet.hip)
+    "uenc_stem7x7_s2_patches": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "uenc_maxpool3x3_s2_fwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_maxpool3x3_s2_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_bn_workspace_floats": [c_l, c_i],
+    "uenc_bn_stats": [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_l, c_p],
+    "uenc_bn_act_fwd": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_f, c_i, c_p],
+    "uenc_bn_act_bwd_reduce": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_l, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_l, c_p],
+    "uenc_bn_act_bwd_apply": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_f, c_i, c_i, c_p],
 }
 
 
@@ -147,6 +156,7 @@ def _load():
     lib.uenc_view_synth_workspace_floats.restype = c_l
     lib.uenc_photo_loss_workspace_floats.restype = c_l
     lib.uenc_dwconv7_bwd_weight_workspace_bytes.restype = c_l
+    lib.uenc_bn_workspace_floats.restype = c_l
     lib.uenc_arch.restype = ctypes.c_char_p
     lib.uenc_arch.argtypes = []
     return lib

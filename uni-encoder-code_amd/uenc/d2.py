@@ -4,8 +4,8 @@ The reference is a Detectron2 plug-in: its classes register into
 are constructed by `build_model(cfg)` from a yacs CfgNode.  When `detectron2` is importable the real
 registries / base classes are used, so the classes here drop into an existing D2 process; otherwise
 this module provides minimal stand-ins with the same names and semantics (Registry, CfgNode with
-`_BASE_` YAML chains, `configurable`, ShapeSpec, Backbone, ImageList, Conv2d, get_norm,
-build_backbone / build_sem_seg_head / build_model).
+`_BASE_` YAML chains, `configurable`, ShapeSpec, Backbone, ImageList, Conv2d, get_norm, FrozenBatchNorm2d,
+CNNBlockBase, build_backbone / build_sem_seg_head / build_model).
 """
 import ast
 import copy
@@ -26,7 +26,7 @@ except Exception:
 
 if HAVE_D2:  # pragma: no cover
     from detectron2.config import CfgNode, configurable, get_cfg
-    from detectron2.layers import Conv2d, ShapeSpec, get_norm
+    from detectron2.layers import CNNBlockBase, Conv2d, FrozenBatchNorm2d, ShapeSpec, get_norm
     from detectron2.modeling import (BACKBONE_REGISTRY, META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, Backbone,
                                      build_backbone, build_model, build_sem_seg_head)
     from detectron2.structures import Boxes, ImageList, Instances
@@ -311,12 +311,74 @@ else:
                 x = self.activation(x)
             return x
 
+    class FrozenBatchNorm2d(nn.Module):
+        """detectron2.layers.FrozenBatchNorm2d: BatchNorm2d whose statistics and affine parameters are fixed buffers
+        (weight, bias, running_mean, running_var; eps 1e-5).  It has no batch counter: a checkpoint's `num_batches_tracked` is dropped
+        on load, one without it loads as well."""
+        _version = 3
+
+        def __init__(self, num_features, eps=1e-5):
+            super().__init__()
+            self.num_features, self.eps = num_features, eps
+            self.register_buffer("weight", torch.ones(num_features))
+            self.register_buffer("bias", torch.zeros(num_features))
+            self.register_buffer("running_mean", torch.zeros(num_features))
+            self.register_buffer("running_var", torch.ones(num_features) - eps)
+
+        def forward(self, x):
+            scale = self.weight * (self.running_var + self.eps).rsqrt()
+            shift = self.bias - self.running_mean * scale
+            return x * scale.to(x.dtype).reshape(1, -1, 1, 1) + shift.to(x.dtype).reshape(1, -1, 1, 1)
+
+        def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+            state_dict.pop(prefix + "num_batches_tracked", None)
+            super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+        def __repr__(self):
+            return f"FrozenBatchNorm2d(num_features={self.num_features}, eps={self.eps})"
+
+        @classmethod
+        def convert_frozen_batchnorm(cls, module):
+            """`module` with every BatchNorm2d / SyncBatchNorm below it (itself included) replaced by a frozen copy."""
+            if isinstance(module, (nn.BatchNorm2d, nn.SyncBatchNorm)):
+                res = cls(module.num_features, module.eps)
+                if module.affine:
+                    res.weight.data = module.weight.data.clone().detach()
+                    res.bias.data = module.bias.data.clone().detach()
+                res.running_mean.data = module.running_mean.data
+                res.running_var.data = module.running_var.data
+                return res
+            for name, child in module.named_children():
+                new_child = cls.convert_frozen_batchnorm(child)
+                if new_child is not child:
+                    module.add_module(name, new_child)
+            return module
+
+    class CNNBlockBase(nn.Module):
+        """detectron2.layers.CNNBlockBase: a block with in_channels / out_channels / stride and detectron2's `freeze()`."""
+
+        def __init__(self, in_channels, out_channels, stride):
+            super().__init__()
+            self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
+
+        def freeze(self):
+            for p in self.parameters():
+                p.requires_grad = False
+            FrozenBatchNorm2d.convert_frozen_batchnorm(self)
+            return self
+
     def get_norm(norm, out_channels):
         if norm is None or (isinstance(norm, str) and len(norm) == 0):
             return None
         if isinstance(norm, str):
             if norm == "GN":
                 return nn.GroupNorm(32, out_channels)
+            if norm == "BN":
+                return nn.BatchNorm2d(out_channels)
+            if norm == "SyncBN":     # same parameters and buffers; the statistics exchange across ranks is the caller's (backbone/resnet.py)
+                return nn.SyncBatchNorm(out_channels)
+            if norm == "FrozenBN":
+                return FrozenBatchNorm2d(out_channels)
             if norm == "LN":     # detectron2's "LN" is a per-pixel channel LayerNorm, NOT GroupNorm(1, C); no shipped config uses it
                 raise NotImplementedError("norm 'LN' (detectron2 channel LayerNorm) is outside the hot path (SURVEY.md §8)")
             raise NotImplementedError(f"norm {norm!r} is outside the hot path (SURVEY.md §8)")

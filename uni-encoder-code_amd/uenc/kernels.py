@@ -1253,3 +1253,106 @@ def layer_scale_grads(dw2p: torch.Tensor, db2p: Optional[torch.Tensor], w2: torc
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N)
     check(lib.uenc_layer_scale_grads(dw2p.data_ptr(), ptr(db2p), w2.data_ptr(), ptr(b2), gamma.data_ptr(), ptr(gw2), ptr(gb2), ptr(ggamma),
                                      N, Kd, stream_ptr()), "layer_scale_grads")
+
+
+# ---- ResNet backbone: stem patch gather, max pooling, BatchNorm + residual + ReLU (csrc/resnet.hip) ----
+def _cl_check(x: torch.Tensor, name: str, ndim: int):
+    if x.dim() != ndim or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda or not x.is_contiguous():
+        raise capi.UencError(f"{name} must be a contiguous {ndim}-D channels-last fp32 | bf16 GPU tensor, got {tuple(x.shape)} {x.dtype}")
+    if x.shape[-1] % 8 != 0:
+        raise ValueError(f"the ResNet kernels need a channel count that is a multiple of 8 (got {x.shape[-1]}); every stock ResNet width "
+                         "satisfies this")
+    return x.shape
+
+
+def _cvec(t: Optional[torch.Tensor], C: int, name: str):
+    assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == C), name
+    return t
+
+
+def stem7x7_s2_patches(x: torch.Tensor) -> torch.Tensor:
+    """x (B, 3, H, W) fp32 NCHW -> (B * Ho * Wo, 152) patch matrix of the 7x7 stride-2 padding-3 convolution in the GEMM operand dtype,
+    (ky, kx, c) column order, 147 columns zero-padded to 152; Ho = (H - 1) // 2 + 1."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise capi.UencError(f"stem7x7_s2_patches: x must be a contiguous (B, 3, H, W) fp32 GPU tensor, got {tuple(x.shape)} {x.dtype}")
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    col = torch.empty((B * Ho * Wo, 152), dtype=adt(), device=x.device)
+    check(lib.uenc_stem7x7_s2_patches(x.data_ptr(), col.data_ptr(), dt(col), B, H, W, stream_ptr()), "stem7x7_s2_patches")
+    return col
+
+
+def maxpool3x3_s2_fwd(x: torch.Tensor):
+    """F.max_pool2d(x, 3, 2, 1) on x (B, H, W, C) channels-last -> (y (B, Ho, Wo, C) in x's dtype, idx uint8: the selected tap)."""
+    B, H, W, C = _cl_check(x, "x", 4)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty((B, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    idx = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=x.device)
+    check(lib.uenc_maxpool3x3_s2_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), dt(x), B, H, W, C, stream_ptr()), "maxpool3x3_s2_fwd")
+    return y, idx
+
+
+def maxpool3x3_s2_bwd(dy: torch.Tensor, idx: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    B, Ho, Wo, C = _cl_check(dy, "dy", 4)
+    assert idx.dtype == torch.uint8 and idx.is_contiguous() and idx.shape == dy.shape and (Ho, Wo) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    dx = torch.empty((B, H, W, C), dtype=dy.dtype, device=dy.device)
+    check(lib.uenc_maxpool3x3_s2_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), dt(dy), B, H, W, C, stream_ptr()), "maxpool3x3_s2_bwd")
+    return dx
+
+
+def _bn_ws(M: int, C: int, device) -> torch.Tensor:
+    return _scratch("bn_slabs", 4 * int(lib.uenc_bn_workspace_floats(M, C)), device)
+
+
+def bn_stats(x2: torch.Tensor, running_mean=None, running_var=None, num_batches_tracked=None, momentum: float = 0.1):
+    """x2 (M, C) -> (mean, biased variance) per channel, fp32; the running statistics (unbiased variance) and the int64 batch counter are
+    updated in place on the device.  One value per channel is refused as torch does."""
+    M, C = _cl_check(x2, "x", 2)
+    if M <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x2.shape)}")
+    _cvec(running_mean, C, "running_mean"); _cvec(running_var, C, "running_var")
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.is_cuda)
+    mean = torch.empty((C,), dtype=torch.float32, device=x2.device)
+    var = torch.empty_like(mean)
+    ws = _bn_ws(M, C, x2.device)
+    check(lib.uenc_bn_stats(x2.data_ptr(), dt(x2), M, C, mean.data_ptr(), var.data_ptr(), ptr(running_mean), ptr(running_var),
+                            ptr(num_batches_tracked), float(momentum), ws.data_ptr(), ws.numel() // 4, stream_ptr()), "bn_stats")
+    return mean, var
+
+
+def bn_act_fwd(x2: torch.Tensor, mean, var, gamma, beta, *, res=None, relu=False, eps: float = 1e-5, out_dtype=torch.float32):
+    """act(x * s + t (+ res)) with s = gamma / sqrt(var + eps), t = beta - mean * s per channel: x2, res (M, C) -> (M, C) out_dtype."""
+    M, C = _cl_check(x2, "x", 2)
+    for t, n in ((mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
+        _cvec(t, C, n)
+    if res is not None:
+        assert _cl_check(res, "res", 2) == x2.shape
+    y = torch.empty((M, C), dtype=out_dtype, device=x2.device)
+    check(lib.uenc_bn_act_fwd(x2.data_ptr(), dt(x2), mean.data_ptr(), var.data_ptr(), ptr(gamma), ptr(beta), ptr(res),
+                              dt(res) if res is not None else 0, y.data_ptr(), dt(y), M, C, float(eps), int(relu), stream_ptr()), "bn_act_fwd")
+    return y
+
+
+def bn_act_bwd(dy2: torch.Tensor, y2: Optional[torch.Tensor], x2: torch.Tensor, mean, var, gamma, *, relu: bool, train: bool, eps: float = 1e-5,
+               dgamma=None, dbeta=None, want_dres: bool = False, dx_dtype=torch.float32, param_sums: bool = True):
+    """Backward of bn_act_fwd -> (dx (M, C) dx_dtype, dres | None: the masked gradient in dy's dtype).  y2: the saved output (the ReLU mask),
+    x2: the saved input.  dgamma / dbeta (fp32, accumulated in place) may be None; the reduction is skipped when neither the
+    parameters (param_sums) nor the batch statistics (train) need it."""
+    M, C = _cl_check(dy2, "dy", 2)
+    assert x2.shape == dy2.shape and (not relu or (y2 is not None and y2.shape == dy2.shape and y2.is_contiguous()))
+    _cl_check(x2, "x", 2)
+    for t, n in ((mean, "mean"), (var, "var"), (gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _cvec(t, C, n)
+    sums = None
+    if train or (param_sums and (dgamma is not None or dbeta is not None)):
+        sums = torch.empty((2, C), dtype=torch.float32, device=dy2.device)
+        ws = _bn_ws(M, C, dy2.device)
+        check(lib.uenc_bn_act_bwd_reduce(dy2.data_ptr(), dt(dy2), ptr(y2), dt(y2) if y2 is not None else 0, x2.data_ptr(), dt(x2),
+                                         mean.data_ptr(), var.data_ptr(), M, C, float(eps), int(relu), sums.data_ptr(), ptr(dgamma), ptr(dbeta),
+                                         ws.data_ptr(), ws.numel() // 4, stream_ptr()), "bn_act_bwd_reduce")
+    dx = torch.empty((M, C), dtype=dx_dtype, device=dy2.device)
+    dres = torch.empty_like(dy2) if want_dres else None
+    check(lib.uenc_bn_act_bwd_apply(dy2.data_ptr(), dt(dy2), ptr(y2), dt(y2) if y2 is not None else 0, x2.data_ptr(), dt(x2), mean.data_ptr(),
+                                    var.data_ptr(), ptr(gamma), ptr(sums), dx.data_ptr(), dt(dx), ptr(dres), dt(dres) if want_dres else 0,
+                                    M, C, float(eps), int(relu), int(train), stream_ptr()), "bn_act_bwd_apply")
+    return dx, dres

@@ -1949,3 +1949,162 @@ class Conv2x2S2Fn(torch.autograd.Function):
 def conv2x2_s2(x_nhwc, weight, bias=None):
     """x (B, H, W, Cin) channels-last -> (B, H // 2, W // 2, Cout) fp32."""
     return Conv2x2S2Fn.apply(x_nhwc, weight, bias)
+
+
+# --------------------------------------------------------------------------------------------
+# ResNet: 7x7 stride-2 stem, 3x3 stride-2 max pooling, conv -> BatchNorm (+ residual) (-> ReLU)
+# --------------------------------------------------------------------------------------------
+class StemConvFn(torch.autograd.Function):
+    """7x7 stride-2 padding-3 convolution of the 3-channel NCHW fp32 image (reference backbone/resnet.py:344-352) as patch gather
+    (csrc/resnet.hip, K = 147 padded to 152) + MFMA GEMM: x (B, 3, H, W) -> (B, Ho, Wo, Cout) fp32 channels-last, Ho = (H - 1) // 2 + 1.
+    The weight gradient is the token-contraction GEMM on the saved patch matrix; the image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("the ResNet stem computes no gradient for the image: pass an input that does not require one")
+        B, _, H, W = x.shape
+        Co = weight.shape[0]
+        if tuple(weight.shape[1:]) != (3, 7, 7) or Co % 8 != 0:
+            raise ValueError(f"stem convolution: weight must be (Cout, 3, 7, 7) with Cout a multiple of 8, got {tuple(weight.shape)}")
+        col = K.stem7x7_s2_patches(x.detach().float().contiguous())
+        out = K.gemm_nt(col, _conv_wmat(weight, "stem7", pad8=True), out_dtype=F32)
+        ctx.save_for_backward(col, weight)
+        return out.view(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Co)
+
+    @staticmethod
+    def backward(ctx, dy):
+        col, weight = ctx.saved_tensors
+        if weight.requires_grad:
+            _conv_wgrad(_conv_dy(dy, col.shape[0], weight.shape[0]), col, weight, None)
+        return None, None
+
+
+def stem_conv7x7_s2(x_nchw, weight):
+    """x (B, 3, H, W) fp32 image -> (B, Ho, Wo, Cout) fp32 channels-last."""
+    return StemConvFn.apply(x_nchw, weight)
+
+
+class MaxPool3x3S2Fn(torch.autograd.Function):
+    """F.max_pool2d(x, 3, 2, 1) on a channels-last map (B, H, W, C) fp32 | bf16; the backward gathers through the saved tap index."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y, idx = K.maxpool3x3_s2_fwd(x if x.is_contiguous() else x.contiguous())
+        ctx.save_for_backward(idx)
+        ctx.hw = (x.shape[1], x.shape[2])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        return K.maxpool3x3_s2_bwd(dy if dy.is_contiguous() else dy.contiguous(), idx, *ctx.hw)
+
+
+def max_pool3x3_s2(x_nhwc):
+    return MaxPool3x3S2Fn.apply(x_nhwc)
+
+
+class BnActFn(torch.autograd.Function):
+    """act(BatchNorm(x) (+ residual)) on rows: x (M, C) fp32 | bf16, act = ReLU or identity (csrc/resnet.hip).  train: batch statistics
+    (the running ones and the batch counter are updated on the device); otherwise running_mean / running_var normalise (eval mode of
+    a BatchNorm, or a FrozenBatchNorm2d whose gamma / beta are buffers).  Saved: x, the output (the ReLU mask), mean, var."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, nbt, relu, train, eps, momentum, out_dtype):
+        x2 = x if x.is_contiguous() else x.contiguous()
+        if train:
+            mean, var = K.bn_stats(x2, running_mean, running_var, nbt, momentum)
+        else:
+            mean, var = running_mean, running_var
+        res2 = None if residual is None else (residual if residual.is_contiguous() else residual.contiguous())
+        y = K.bn_act_fwd(x2, mean, var, gamma.detach(), beta.detach(), res=res2, relu=relu, eps=eps, out_dtype=K._odt(out_dtype))
+        ctx.save_for_backward(x2, y if relu else None, mean, var, gamma, beta)
+        ctx.cfg = (relu, train, eps, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, y, mean, var, gamma, beta = ctx.saved_tensors
+        relu, train, eps, has_res = ctx.cfg
+        dy2 = dy if dy.is_contiguous() else dy.contiguous()
+        want_res = has_res and ctx.needs_input_grad[1]
+        dx, dres = K.bn_act_bwd(dy2, y, x2, mean, var, gamma.detach(), relu=relu, train=train, eps=eps,
+                                dgamma=grad_buf(gamma) if gamma.requires_grad else None, dbeta=grad_buf(beta) if beta.requires_grad else None,
+                                want_dres=want_res and relu, dx_dtype=K.adt())
+        if want_res and not relu:
+            dres = dy2
+        if gamma.requires_grad or beta.requires_grad:
+            _tn_notify(gamma, beta)
+        return (dx, dres) + (None,) * 10
+
+
+def bn_act(x2, gamma, beta, running_mean, running_var, nbt=None, *, residual=None, relu=False, train=False, eps=1e-5, momentum=0.1,
+           out_dtype=F32):
+    if x2.shape[-1] % 8 != 0:
+        raise ValueError(f"BatchNorm kernels: the channel count must be a multiple of 8 (got {x2.shape[-1]})")
+    return BnActFn.apply(x2, residual, gamma, beta, running_mean, running_var, nbt, relu, train, eps, momentum, out_dtype)
+
+
+class ConvBnActFn(torch.autograd.Function):
+    """conv -> BatchNorm (+ residual) (-> ReLU) as ONE autograd node (reference backbone/resnet.py: every Conv2d carries its norm, the
+    blocks add the shortcut and apply ReLU).  kind "stem": the 7x7 stride-2 convolution of the NCHW image; kind 1 / 3: a 1x1 / 3x3
+    convolution (stride 1 | 2, no bias) of a channels-last map (B, H, W, Cin).  The convolution is StemConvFn / LinearFn / Conv3x3Fn /
+    ConvS2Fn run in place (fp32 result, which is also what the backward's x-hat is recomputed from), the rest is BnActFn; between the two
+    the gradient stays in the GEMM operand dtype.  -> (B, Ho, Wo, Cout) in out_dtype."""
+
+    @staticmethod
+    def _conv(kind, stride):
+        if kind == "stem":
+            return StemConvFn
+        if kind == 1:
+            return LinearFn
+        return Conv3x3Fn if stride == 1 else ConvS2Fn
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, gamma, beta, running_mean, running_var, nbt, kind, stride, relu, train, eps, momentum, out_dtype):
+        Co = weight.shape[0]
+        fn = ConvBnActFn._conv(kind, stride)
+        need = ctx.needs_input_grad[0]
+        if fn is StemConvFn:
+            ca = _SubCtx((need, False))
+            z = StemConvFn.forward(ca, x, weight)
+        elif fn is LinearFn:
+            ca = _SubCtx((need, False, False, False, False, False))
+            z = LinearFn.forward(ca, x if stride == 1 else x[:, ::stride, ::stride].contiguous(), weight, None, None, None, F32)
+        elif fn is Conv3x3Fn:
+            ca = _SubCtx((need, False))
+            z = Conv3x3Fn.forward(ca, x, weight).view(x.shape[0], x.shape[1], x.shape[2], Co)
+        else:
+            ca = _SubCtx((need, False, False))
+            z = ConvS2Fn.forward(ca, x, weight, None)
+        B, Ho, Wo = z.shape[:3]
+        cb = _SubCtx((True, ctx.needs_input_grad[1]) + (False,) * 10)
+        y = BnActFn.forward(cb, z.reshape(B * Ho * Wo, Co), None if residual is None else residual.reshape(B * Ho * Wo, Co), gamma, beta,
+                            running_mean, running_var, nbt, relu, train, eps, momentum, out_dtype)
+        _save_inner(ctx, ca, cb)
+        ctx.geom = (kind, stride, tuple(x.shape), (B, Ho, Wo, Co), None if residual is None else tuple(residual.shape))
+        return y.view(B, Ho, Wo, Co)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ca, cb = _inner(ctx)
+        kind, stride, xshape, (B, Ho, Wo, Co), rshape = ctx.geom
+        g = BnActFn.backward(cb, dy.reshape(B * Ho * Wo, Co))
+        fn = ConvBnActFn._conv(kind, stride)
+        dz = g[0].view(B, Ho * Wo, Co) if fn is Conv3x3Fn else g[0].view(B, Ho, Wo, Co)
+        dx = fn.backward(ca, dz)[0]
+        if dx is not None and fn is LinearFn and stride != 1:
+            full = dx.new_zeros(xshape)
+            full[:, ::stride, ::stride] = dx
+            dx = full
+        dres = None if g[1] is None else g[1].view(rshape)
+        return (dx, dres) + (None,) * 13
+
+
+def conv_bn_act(x, weight, bn, *, kind, stride=1, residual=None, relu=False, train=False, out_dtype=F32):
+    """bn: an nn.BatchNorm2d (train: batch statistics when `train`) or a d2.FrozenBatchNorm2d (weight / bias are buffers)."""
+    if weight.shape[0] % 8 != 0 or (kind != "stem" and weight.shape[1] % 8 != 0):
+        raise ValueError(f"ResNet convolutions need channel counts that are multiples of 8, got weight {tuple(weight.shape)}")
+    return ConvBnActFn.apply(x, residual, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, getattr(bn, "num_batches_tracked", None),
+                             kind, stride, relu, train, bn.eps, getattr(bn, "momentum", 0.1), out_dtype)
