@@ -76,7 +76,7 @@ def test_na2d_ignores_retired_switches(U, monkeypatch):
     UENC_NA2D_NT (used to override the MFMA kernels' tiles per workgroup; the planner gives nt = 1 at this size, so 3 would change
     the grid) are no longer read: with either set, out, lse and dqkv (no atomics) are bit-identical to the run without them.
     drpb is summed with float atomics: within the oracle bound of test_na2d_kernels_vs_oracle, and within 1e-4 of the unset run
-    relative to its largest entry (the bound test_window_attention_bwd_kernel_forms_agree puts on its atomically summed gradients)."""
+    relative to its largest entry (the bound this suite puts on atomically summed gradients of two runs of the same arithmetic)."""
     from oracle import dinat_ref as D
     from uenc import kernels as K
     B, H, W, nH, ks, d = 1, 33, 45, 3, 7, 2

@@ -1,6 +1,6 @@
 """Window-attention kernel timing on the Swin-L stage shapes (GPU box)."""
 import os, sys, torch
-sys.path.insert(0, '/root/repo/uni-encoder-code_amd')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uni-encoder-code_amd"))
 from uenc import kernels as K
 
 def timeit(fn, n=5):

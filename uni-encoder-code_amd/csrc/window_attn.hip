@@ -28,7 +28,6 @@
 // Algorithmic HBM bytes per token per head: fwd read 3*64 + write 64; bwd read 5*64 + write 3*64.
 #include "common.h"
 #include "lds_frag.h"
-#include <stdlib.h>
 #include <type_traits>
 
 #define LOG2E 1.4426950408889634f
@@ -50,7 +49,6 @@ struct WAttn {
     float* dpad;            // (3C) q|k|v bias gradient that reaches the heads through padding slots: ADDED (atomics) to the caller's buffer
     int B, H, W, C, nH, ws, shift, Hp, Wp, nWw, nWin, nWinTotal, N;
     float scale;
-    int variant;            // UENC_WATTN_VARIANT (A/B switches, 0 in production)
 };
 
 template <int NTILES>
@@ -128,15 +126,16 @@ __device__ __forceinline__ void stage_images(unsigned char* const (&img)[NIMG], 
         }
 }
 
-// LDSB (12 x 12 windows): the bias comes from a 529-entry LDS copy of the head's table (gathered from the dense bias while the q / k / v
+// 12 x 12 windows (WS12): the bias comes from a 529-entry LDS copy of the head's table (gathered from the dense bias while the q / k / v
 // rows are in flight) instead of 83 KB of dense [q][key] rows per window-head -- three times the bytes of its q, k and v.  Same values.
-template <int NTILES, bool LDSB>
+// Smaller windows read the dense bias rows from L2.
+template <int NTILES>
 __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
-    static_assert(!LDSB || NTILES == 9, "the LDS bias table is laid out for ws = 12");
+    constexpr bool WS12 = NTILES == 9;                 // the LDS bias table is laid out for ws = 12
     using Cf = WCfg<NTILES>;
     constexpr int NTH = Cf::NTH, NP = Cf::NP, NKB = Cf::NKB, NK2 = Cf::NK2;
-    constexpr int OFF_BT = (3 * NK2 * 64 + NK2 * 4 + NK2 + 15) / 16 * 16;      // LDSB: float rev[532], rev[528 - t] = log2(e) * table[t][head]
-    __shared__ __attribute__((aligned(16))) unsigned char smem[OFF_BT + (LDSB ? 532 * 4 : 0)];
+    constexpr int OFF_BT = (3 * NK2 * 64 + NK2 * 4 + NK2 + 15) / 16 * 16;      // WS12: float rev[532], rev[528 - t] = log2(e) * table[t][head]
+    __shared__ __attribute__((aligned(16))) unsigned char smem[OFF_BT + (WS12 ? 532 * 4 : 0)];
     unsigned char* Qs = smem;
     unsigned char* Ks = smem + NK2 * 64;
     unsigned char* Vs = smem + 2 * NK2 * 64;
@@ -152,15 +151,15 @@ __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
     const int C = p.C, hoff = head * 32;
     const long C3 = 3 * (long)p.C;
 
-    float tabv = 0.f;                                  // LDSB: table entry t = threadIdx.x = (dy + 11) * 23 + dx + 11, from q = (max(dy,0), max(dx,0)), key = q - (dy,dx)
-    if constexpr (LDSB) {
+    float tabv = 0.f;                                  // WS12: table entry t = threadIdx.x = (dy + 11) * 23 + dx + 11, from q = (max(dy,0), max(dx,0)), key = q - (dy,dx)
+    if constexpr (WS12) {
         if (threadIdx.x < 529) {
             const int t = threadIdx.x, dy = t / 23 - 11, dx = t % 23 - 11;
             const int qy = dy > 0 ? dy : 0, qx = dx > 0 ? dx : 0;
             tabv = p.bias_q[((long)head * NP + qy * 12 + qx) * NP + (qy - dy) * 12 + (qx - dx)];
         }
     }
-    window_slots<NK2, NTILES == 9>(p, b, wi, wj, tokoff, rid, nullptr, NTH);
+    window_slots<NK2, WS12>(p, b, wi, wj, tokoff, rid, nullptr, NTH);
     __syncthreads();
     {
         unsigned char* const img[3] = {Qs, Ks, Vs};
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
         const bf16* const pad[3] = {p.qkv_bias + hoff, p.qkv_bias + C + hoff, p.qkv_bias + 2 * C + hoff};
         stage_images<3, NK2, NTH>(img, base, stride, pad, tokoff);
     }
-    if constexpr (LDSB) {
+    if constexpr (WS12) {
         if (threadIdx.x < 529) ((float*)(smem + OFF_BT))[528 - threadIdx.x] = tabv;
     }
     __syncthreads();
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
 #pragma unroll
     for (int kt = 0; kt < NTILES; ++kt) {
         float4 bb;
-        if constexpr (LDSB) {
+        if constexpr (WS12) {
             const int key0 = kt * 16 + 4 * fg;
             const float* rb = revq + (key0 / 12) * 23 + key0 % 12;
             bb = make_float4(rb[0], rb[1], rb[2], rb[3]);
@@ -253,7 +252,7 @@ __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
 // Persistent: the grid is nH x G workgroups, workgroup (head, g) walks windows g, g + G, ... of its head.
 //   * the q/k/v/dO rows of the NEXT window go global -> LDS by LDS-DMA (global_load_lds_dwordx4, lane-linear destination,
 //     XOR swizzle applied to the per-lane source chunk) into the second of two stages while the current window is
-//     computed; its saved forward output rows (for delta) are prefetched into registers;
+//     computed; its saved forward output rows (for delta) are prefetched into registers (12 x 12: staged as a fifth image);
 //   * the relative-position-table gradient is NOT scattered per window (LDS float atomics cost ~3 cycles per lane:
 //     20k of them per window-head were two thirds of this kernel): dS is the same accumulator tile for every window, so
 //     it is summed over the workgroup's windows in registers and written once as a dense [q][key] partial;
@@ -261,40 +260,44 @@ __global__ __launch_bounds__(64 * NTILES) void wattn_fwd_kernel(WAttn p) {
 __device__ __attribute__((aligned(16))) unsigned int g_wattn_zero16[4];      // a 16-byte chunk of zeros (rows beyond N, dO pad rows)
 __device__ float g_wattn_big = 1e30f;                                        // "row statistic" of a slot without a token: exp2(s - 1e30) = 0
 
-//   * LDSB (12 x 12 windows): the relative-position bias of phase A is looked up in a 529-entry LDS copy of the head's table
-//     instead of being loaded as dense [q][key] rows from L2 (83 KB per window-head, more than its q / k / v / dO): an ordinary
-//     global load whose result is used while the next window's LDS-DMA is in flight makes the wave wait for vmcnt(0), i.e. for
-//     that whole DMA, in the middle of phase A (loads retire in order).  Same values, bit-identical results.
-//   * LOADER: a TENTH wave does nothing but the slot bookkeeping and the LDS-DMA of the next window.  In-kernel s_memtime stamps
+// Windows of up to 128 slots (NTILES <= 8): one wave per 16-token tile.  Every wave issues its share of the next window's DMA right behind
+// the top barrier, prefetches its saved-output row and the dense [q][key] bias rows of phase A from L2, and recomputes the row statistics.
+// 12 x 12 windows (WS12, NTILES == 9) run differently in three ways:
+//   * the relative-position bias of phase A is looked up in a 529-entry LDS copy of the head's table instead of being loaded as dense
+//     [q][key] rows from L2 (83 KB per window-head, more than its q / k / v / dO): an ordinary global load whose result is used while
+//     the next window's LDS-DMA is in flight makes the wave wait for vmcnt(0), i.e. for that whole DMA, in the middle of phase A (loads
+//     retire in order).  Same values, bit-identical results.
+//   * a TENTH wave, the loader, does nothing but the slot bookkeeping and the LDS-DMA of the next window.  In-kernel s_memtime stamps
 //     (profiles/r03_wattn_bwd_experiments.txt) showed every compute wave spending 16 % of a window inside its share of the DMA issue
 //     (4-5 scattered 1 KB global_load_lds each, all nine waves through the CU's one address path at once) and 7 % in the slot
 //     arithmetic, and then waiting vmcnt(0) for its own DMA in the middle of phase A (loads retire in order behind the DMA).  With
-//     the loader the compute waves issue no DMA at all: their only vector-memory operations are the saved-output prefetch and the
-//     result stores.  The loader takes part in the three barriers of a window: stage landed (its vmcnt(0)) -> top barrier -> slots +
-//     DMA of the NEXT window into the other stage (free since the previous end barrier) -> mid barrier (the slots become visible:
-//     the compute waves prefetch their next saved-output rows) -> end barrier.
-//   * LSE (with LOADER): the forward saved the row statistics; the loader brings the 144 values of a window by three 4-byte-per-lane
-//     LDS-DMA instructions and phase A computes P = exp2(s - lse) directly: no running maximum, no sum, no reciprocal, no cross-lane
-//     butterflies (about a quarter of phase A's VALU instructions; the phases' time follows their VALU count).
-template <int NTILES, bool LDSB, bool LOADER, bool LSE = false>
-__global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_kernel(WAttn p, int G) {
-    static_assert(!LDSB || NTILES == 9, "the LDS bias table is laid out for ws = 12 (N = NP = 144, key quads never straddle a window row)");
-    static_assert(!LSE || LOADER, "the saved row statistics come in through the loader wave");
+//     the loader the compute waves issue no DMA at all: their only vector-memory operations are the result stores (the saved forward
+//     output comes in as a fifth image).  The loader takes part in the three barriers of a window: stage landed (its vmcnt(0)) -> top
+//     barrier -> DMA of the NEXT window into the other stage (free since the previous end barrier) -> mid barrier -> slots of the window
+//     after next -> end barrier.
+//   * LSE: the forward saved the row statistics; the loader brings the 144 values of a window by three 4-byte-per-lane LDS-DMA
+//     instructions and phase A computes P = exp2(s - lse) directly: no running maximum, no sum, no reciprocal, no cross-lane
+//     butterflies (about a quarter of phase A's VALU instructions; the phases' time follows their VALU count).  !LSE: no statistics
+//     were given and phase A recomputes them.
+template <int NTILES, bool LSE = false>
+__global__ __launch_bounds__(64 * (NTILES + (NTILES == 9 ? 1 : 0))) void wattn_bwd_kernel(WAttn p, int G) {
+    constexpr bool WS12 = NTILES == 9;                 // the LDS bias table is laid out for ws = 12 (N = NP = 144, key quads never straddle a window row)
+    static_assert(!LSE || NTILES == 9, "the saved row statistics come in through the loader wave");
     using Cf = WCfg<NTILES>;
-    constexpr int NWAVES = NTILES + (LOADER ? 1 : 0), NTH = 64 * NWAVES;
+    constexpr int NWAVES = NTILES + (WS12 ? 1 : 0), NTH = 64 * NWAVES;
     constexpr int NP = Cf::NP, NKB = Cf::NKB, NK2 = Cf::NK2;
-    constexpr int NIMG = LOADER ? 5 : 4;               // q, k, v, dO (+ LOADER: the saved forward output O, for delta)
+    constexpr int NIMG = WS12 ? 5 : 4;                 // q, k, v, dO (+ WS12: the saved forward output O, for delta)
     constexpr int IMG = NK2 * 64, STAGE = NIMG * IMG;
-    constexpr int NTB = LOADER ? 3 : 2;                // slot buffers: LOADER keeps the window after next ready as well
+    constexpr int NTB = WS12 ? 3 : 2;                  // slot buffers: the loader keeps the window after next ready as well
     constexpr int OFF_TOK = 2 * STAGE;                 // int tokoff[NTB][NK2]
     constexpr int OFF_RID = OFF_TOK + NTB * NK2 * 4;   // u8  rid[NTB][NK2]
     constexpr int OFF_DEL = (OFF_RID + NTB * NK2 + 15) / 16 * 16;   // float delta[NK2]
     constexpr int OFF_PAD = OFF_DEL + NK2 * 4;         // float padacc[96]
     constexpr int OFF_P = OFF_PAD + 96 * 4;            // bf16 P[key tile][NK2 query rows][16 keys]: the softmax of phase A, read back
     constexpr int PSUB = NK2 * 32;                     //   transposed (ds_read_b64_tr_b16) as the P / dS operand tiles of phase B
-    constexpr int OFF_BT = OFF_P + NTILES * PSUB;      // LDSB: float rev[532], rev[528 - t] = log2(e) * table[t][head]
+    constexpr int OFF_BT = OFF_P + NTILES * PSUB;      // WS12: float rev[532], rev[528 - t] = log2(e) * table[t][head]
     constexpr int OFF_LSE = OFF_BT + 532 * 4;          // LSE: float lse_s[2 stages][192]: the saved row statistics of the window's queries
-    constexpr int OFF_MF = OFF_LSE + 1536;             // LOADER: int mflag[4]: "this window takes the shift mask", per slot buffer (written with the slots)
+    constexpr int OFF_MF = OFF_LSE + 1536;             // WS12: int mflag[4]: "this window takes the shift mask", per slot buffer (written with the slots)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* delta = (float*)(smem + OFF_DEL);
     float* padacc = (float*)(smem + OFF_PAD);          // [3][32] q|k|v bias gradient from padding slots, summed over this WG's windows
@@ -316,21 +319,21 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     typedef __attribute__((address_space(3))) void lds_void;
 
-    const bool loader = LOADER && wave == NTILES;
+    const bool loader = WS12 && wave == NTILES;
     auto slots = [&](int win, int st) {                // st: slot buffer
         const int b = win / p.nWin, wrem = win - b * p.nWin;
         const int wi = wrem / p.nWw, wj = wrem - wi * p.nWw;
-        if (LOADER) {
-            window_slots<NK2, NTILES == 9>(p, b, wi, wj, (int*)(smem + OFF_TOK) + st * NK2, smem + OFF_RID + st * NK2, nullptr, 64, lane);
+        if (WS12) {
+            window_slots<NK2, true>(p, b, wi, wj, (int*)(smem + OFF_TOK) + st * NK2, smem + OFF_RID + st * NK2, nullptr, 64, lane);
             // the compute waves read the flag instead of repeating the three integer divisions of the window decode (~500 cycles per window)
             if (lane == 0) ((int*)(smem + OFF_MF))[st] = p.shift > 0 && (wi == p.Hp / p.ws - 1 || wj == p.nWw - 1);
-        } else window_slots<NK2, NTILES == 9>(p, b, wi, wj, (int*)(smem + OFF_TOK) + st * NK2, smem + OFF_RID + st * NK2, nullptr, NTH);
+        } else window_slots<NK2>(p, b, wi, wj, (int*)(smem + OFF_TOK) + st * NK2, smem + OFF_RID + st * NK2, nullptr, NTH);
     };
     // LDS-DMA of one window's q, k, v, dO images: 16 rows (1 KB) per wave instruction
     auto issue = [&](int st, int tb) {                 // st: stage, tb: slot buffer
         const int* tok = (const int*)(smem + OFF_TOK) + tb * NK2;
         constexpr int PER_IMG = NK2 / 16;
-        if constexpr (LOADER) {
+        if constexpr (WS12) {
             // The loader wave: all five images of a 16-row block from one slot read.  Sources are a UNIFORM base per image plus a 32-bit
             // byte offset per lane (scalar-base addressing: no 64-bit address arithmetic per instruction), token rows and padding slots
             // as two exec-masked instruction groups (the second one is skipped by all but the windows on the map's edges); the rows
@@ -384,11 +387,11 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
         }
     };
 
-    // LDSB: entry t = (dy + 11) * 23 + dx + 11 of the head's table, gathered from the dense bias (q = (max(dy,0), max(dx,0)), key = q - (dy,dx))
+    // WS12: entry t = (dy + 11) * 23 + dx + 11 of the head's table, gathered from the dense bias (q = (max(dy,0), max(dx,0)), key = q - (dy,dx))
     // and stored REVERSED: the four keys 4 fg .. 4 fg + 3 of a lane sit in one window row, so their entries are four consecutive floats
     const float* rev = (const float*)(smem + OFF_BT);
     int jb[NTILES];                                    // rev index of (this lane's query, key 16 kt + 4 fg): the same for every window
-    if constexpr (LDSB) {
+    if constexpr (WS12) {
         for (int t = threadIdx.x; t < 529; t += NTH) {
             const int dy = t / 23 - 11, dx = t % 23 - 11;
             const int qy = dy > 0 ? dy : 0, qx = dx > 0 ? dx : 0;
@@ -406,7 +409,7 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
     for (int kt = 0; kt < NTILES; ++kt) dsacc[kt] = zero4;
     for (int t = threadIdx.x; t < 96; t += NTH) padacc[t] = 0.f;
     for (int t = threadIdx.x; t < NTILES * PSUB / 16; t += NTH) ((u32x4*)Pimg)[t] = (u32x4){0u, 0u, 0u, 0u};     // rows >= NP are never written
-    if constexpr (LOADER) {                            // rows NP .. NK2 - 1 of every staged image: zero for good (the loader writes rows < NP only)
+    if constexpr (WS12) {                              // rows NP .. NK2 - 1 of every staged image: zero for good (the loader writes rows < NP only)
         constexpr int TAIL = (NK2 - NP) * 4;           // 16-byte chunks per image
         for (int t = threadIdx.x; t < 2 * NIMG * TAIL; t += NTH)
             *(u32x4*)(smem + (t / TAIL) * IMG + NP * 64 + (t % TAIL) * 16) = (u32x4){0u, 0u, 0u, 0u};
@@ -419,7 +422,7 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
         for (int j = 0; j < 8; ++j) o_next[j] = (bf16)0.f;
     }
     if (win < p.nWinTotal) {
-        if (LOADER) {
+        if (WS12) {
             if (loader) {
                 slots(win, 0);                         // written and read back by the same wave: LDS operations of a wave execute in order
                 issue(0, 0);
@@ -431,17 +434,16 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
             __syncthreads();
             issue(0, 0);
         }
-        if (!LOADER) {
+        if (!WS12) {
             const int qtok = ((const int*)(smem + OFF_TOK))[wave * 16 + fr];
             if (qtok >= 0) o_next = *(const bf16x8*)(p.o_saved + (long)qtok * C + hoff + 8 * fg);
         }
     }
-    const bool wait_at_top = (p.variant & 1) != 0;          // bit 0: the round-2 placement of the stage wait (A/B)
-    // LOADER: the waves talk through LDS only, so a barrier needs this wave's LDS operations done (lgkmcnt) and nothing else; __syncthreads()
+    // WS12: the waves talk through LDS only, so a barrier needs this wave's LDS operations done (lgkmcnt) and nothing else; __syncthreads()
     // would also drain vmcnt wherever an LDS-DMA may be outstanding -- the loader would wait for the DMA it has just issued and the compute
     // waves for the acknowledgement of their result stores, at every barrier
     auto wg_barrier = [&]() {
-        if (LOADER) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (WS12) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else __syncthreads();
     };
     // The loader's loop is separate code: with the LDS-DMA in the compute loop's control flow the compiler must assume one is outstanding
@@ -466,11 +468,11 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
         const unsigned char* Ks = Qs + IMG;
         const unsigned char* Vs = Qs + 2 * IMG;
         const unsigned char* dOs = Qs + 3 * IMG;
-        const int tbuf = LOADER ? it % 3 : st;
+        const int tbuf = WS12 ? it % 3 : st;
         const int* tokoff = (const int*)(smem + OFF_TOK) + tbuf * NK2;
         const unsigned char* rid = smem + OFF_RID + tbuf * NK2;
         bool masked;
-        if constexpr (LOADER) {
+        if constexpr (WS12) {
             masked = __builtin_amdgcn_readfirstlane(((const int*)(smem + OFF_MF))[it % 3]) != 0;
         } else {
             const int b = win / p.nWin, wrem = win - b * p.nWin;
@@ -483,18 +485,18 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
         // (all NTILES at once would be 36 more live registers than the 168 a 9-wave workgroup can have)
         const float* brow0 = p.bias_q + ((long)head * NP + wave * 16 + fr) * NP + 4 * fg;
         float4 bnext[3];
-        if constexpr (!LDSB) {
+        if constexpr (!WS12) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) bnext[j] = *(const float4*)(brow0 + (j < NTILES ? j : 0) * 16);
         }
-        if (!LOADER && more) slots(win + G, st ^ 1);
+        if (!WS12 && more) slots(win + G, st ^ 1);
         // This wave's share of the current stage has landed: for the first window by the wait here; for the others by the wait in
         // front of the previous window's dK / dV stores (below).  A wave's vector-memory operations retire in order, so a vmcnt(0)
         // HERE would also wait for those stores to be acknowledged -- with one workgroup per CU nothing else runs meanwhile.
-        if (!LOADER && (it == 0 || wait_at_top)) __builtin_amdgcn_s_waitcnt(0x0f70);
+        if (!WS12 && it == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
         const bf16x8 ov_reg = o_next;
         wg_barrier();                                  // ... everyone's; next window's slots are visible
-        if (!LOADER && more) {
+        if (!WS12 && more) {
             issue(st ^ 1, st ^ 1);
             const int qtok_n = ((const int*)(smem + OFF_TOK))[(st ^ 1) * NK2 + wave * 16 + fr];
             if (qtok_n >= 0) o_next = *(const bf16x8*)(p.o_saved + (long)qtok_n * C + hoff + 8 * fg);
@@ -506,7 +508,7 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
             const int qtok = tokoff[qi];
             const bf16x8 qf = frag_rows(Qs, qt * 16, fr, fg);
             const bf16x8 dof = frag_rows(dOs, qt * 16, fr, fg);
-            const bf16x8 ov = LOADER ? frag_rows(Qs + 4 * IMG, qt * 16, fr, fg) : ov_reg;      // the same 8 channels of the saved output row (zeros for padding slots)
+            const bf16x8 ov = WS12 ? frag_rows(Qs + 4 * IMG, qt * 16, fr, fg) : ov_reg;      // the same 8 channels of the saved output row (zeros for padding slots)
             float dl = 0.f;                               // delta[q] = sum_d dO[q][d] * O[q][d]
             if (qtok >= 0) {
 #pragma unroll
@@ -520,7 +522,7 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
 #pragma unroll
             for (int k3 = 0; k3 < NTILES; k3 += 3) {
                 float4 bcur[3];
-                if constexpr (LDSB) {
+                if constexpr (WS12) {
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
                         const float* rb = rev + jb[k3 + j < NTILES ? k3 + j : 0];
@@ -665,7 +667,7 @@ __global__ __launch_bounds__(64 * (NTILES + (LOADER ? 1 : 0))) void wattn_bwd_ke
             // the next window's q / k / v / dO rows (LDS-DMA issued at the top of this iteration) have had both phases to land: waiting for
             // them here, BEFORE this window's last stores enter the queue, costs nothing and leaves the stores to drain under the next
             // window's phase A
-            if (!LOADER && !wait_at_top) __builtin_amdgcn_s_waitcnt(0x0f70);
+            if (!WS12) __builtin_amdgcn_s_waitcnt(0x0f70);
             if (ktok != -2) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
@@ -858,7 +860,6 @@ static int fill_params(WAttn& p, const void* qkv, const void* qkv_bias, const fl
     p.Hp = (H + ws - 1) / ws * ws; p.Wp = (W + ws - 1) / ws * ws;
     p.nWw = p.Wp / ws; p.nWin = (p.Hp / ws) * p.nWw; p.nWinTotal = B * p.nWin; p.N = ws * ws;
     p.scale = scale;
-    { const char* e = getenv("UENC_WATTN_VARIANT"); p.variant = e ? atoi(e) : 0; }
     p.out = nullptr; p.lse = nullptr; p.o_saved = nullptr; p.d_out = nullptr; p.dqkv = nullptr; p.dtab_ws = nullptr; p.dpad = nullptr;
     return UENC_OK;
 }
@@ -866,11 +867,7 @@ static int fill_params(WAttn& p, const void* qkv, const void* qkv_bias, const fl
 template <int NT>
 static void launch_fwd(const WAttn& p, hipStream_t stream) {
     const unsigned grid = (unsigned)((p.nWinTotal + 7) / 8 * 8 * p.nH);
-    constexpr bool HAS_LDSB = NT == 9;
-    if (HAS_LDSB && !(p.variant & 2))                  // bit 1 of UENC_WATTN_VARIANT: dense bias rows from L2 (A/B)
-        hipLaunchKernelGGL((wattn_fwd_kernel<NT, HAS_LDSB>), dim3(grid), dim3(64 * NT), 0, stream, p);
-    else
-        hipLaunchKernelGGL((wattn_fwd_kernel<NT, false>), dim3(grid), dim3(64 * NT), 0, stream, p);
+    hipLaunchKernelGGL(wattn_fwd_kernel<NT>, dim3(grid), dim3(64 * NT), 0, stream, p);
 }
 // groups per head: ~one resident workgroup per CU for the 9-wave (12 x 12) case, more for small windows
 static int wattn_bwd_groups(int nWinTotal, int nH, int ntiles) {
@@ -886,32 +883,27 @@ static int launch_bwd(const WAttn& p, float* dtab, int defer_dtable, hipStream_t
     using Cf = WCfg<NT>;
     constexpr int NK2 = Cf::NK2;
     const int G = wattn_bwd_groups(p.nWinTotal, p.nH, NT);
+    constexpr bool WS12 = NT == 9;
     constexpr size_t shm = ((size_t)2 * 4 * NK2 * 64 + 2 * NK2 * 4 + 2 * NK2 + 15) / 16 * 16 + NK2 * 4 + 96 * 4 + (size_t)NT * NK2 * 32 + 532 * 4;
-    constexpr bool HAS_LDSB = NT == 9;
     constexpr size_t shm_loader = shm + (size_t)2 * NK2 * 64 + NK2 * 4 + NK2 + 16 + 1536 + 16;      // + the fifth image of both stages, the third slot buffer, the row statistics, the mask flags
+    constexpr size_t lds = WS12 ? shm_loader : shm;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e == hipSuccess && HAS_LDSB) {
-            e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT, HAS_LDSB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        hipError_t e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if constexpr (WS12) {
             if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT, HAS_LDSB, HAS_LDSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_loader);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT, HAS_LDSB, HAS_LDSB, HAS_LDSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_loader);
+                e = hipFuncSetAttribute((const void*)wattn_bwd_kernel<NT, WS12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         }
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
     const int npair = (p.nH + 1) / 2;
     const unsigned grid = (unsigned)((2 * npair * G + 15) / 16 * 16);
-    if (HAS_LDSB && !(p.variant & 14) && p.lse != nullptr)      // 12 x 12 windows: LDS bias table, loader wave, saved row statistics
-        hipLaunchKernelGGL((wattn_bwd_kernel<NT, HAS_LDSB, HAS_LDSB, HAS_LDSB>), dim3(grid), dim3(64 * (NT + 1)), shm_loader, stream, p, G);
-    else if (HAS_LDSB && !(p.variant & 6))             // no statistics given, or bit 3 of UENC_WATTN_VARIANT: recomputed (A/B)
-        hipLaunchKernelGGL((wattn_bwd_kernel<NT, HAS_LDSB, HAS_LDSB>), dim3(grid), dim3(64 * (NT + 1)), shm_loader, stream, p, G);
-    else if (HAS_LDSB && !(p.variant & 2))             // bit 2 of UENC_WATTN_VARIANT: every wave issues its share of the DMA (A/B)
-        hipLaunchKernelGGL((wattn_bwd_kernel<NT, HAS_LDSB, false>), dim3(grid), dim3(64 * NT), shm, stream, p, G);
-    else                                               // bit 1: dense bias rows from L2 as well (A/B)
-        hipLaunchKernelGGL((wattn_bwd_kernel<NT, false, false>), dim3(grid), dim3(64 * NT), shm, stream, p, G);
+    const dim3 block(64 * (NT + (WS12 ? 1 : 0)));       // 12 x 12 windows: the loader wave
+    if (WS12 && p.lse != nullptr)                       // saved row statistics given; otherwise phase A recomputes them
+        hipLaunchKernelGGL((wattn_bwd_kernel<NT, WS12>), dim3(grid), block, lds, stream, p, G);
+    else
+        hipLaunchKernelGGL(wattn_bwd_kernel<NT>, dim3(grid), block, lds, stream, p, G);
     if (!defer_dtable)
         hipLaunchKernelGGL(wattn_dtable_kernel<NT>, dim3((unsigned)(p.nH * NT)), dim3(256), 0, stream, (const float*)p.dtab_ws, dtab, G,
                            p.nH, p.ws);
@@ -946,19 +938,21 @@ extern "C" int uenc_window_attn_fwd(const void* qkv, const void* qkv_bias, const
     UENC_LAUNCH_RET();
 }
 
-// Workgroup groups per head of uenc_window_attn_bwd (the G of its dense dS partials [nH][G][ntiles][NP * 16]); ntiles = uenc_window_attn_np(ws) / 16.
-extern "C" int uenc_window_attn_bwd_groups(int B, int H, int W, int nH, int ws) {
+// G of uenc_window_attn_bwd for this geometry, 0 for arguments it would reject
+static int wattn_bwd_groups_checked(int B, int H, int W, int nH, int ws) {
     if (!(B > 0 && H > 0 && W > 0 && nH > 0 && ws >= 1 && ws <= 12)) return 0;
     const long nwin = (long)B * ((H + ws - 1) / ws) * ((W + ws - 1) / ws);
     return wattn_bwd_groups((int)nwin, nH, wattn_ntiles(ws));
 }
 
+// Workgroup groups per head of uenc_window_attn_bwd (the G of its dense dS partials [nH][G][ntiles][NP * 16]); ntiles = uenc_window_attn_np(ws) / 16.
+extern "C" int uenc_window_attn_bwd_groups(int B, int H, int W, int nH, int ws) { return wattn_bwd_groups_checked(B, H, W, nH, ws); }
+
 // Scratch floats for the dense dS partials of uenc_window_attn_bwd.
 extern "C" long uenc_window_attn_bwd_ws_floats(int B, int H, int W, int nH, int ws) {
-    if (!(B > 0 && H > 0 && W > 0 && nH > 0 && ws >= 1 && ws <= 12)) return 0;
-    const long nwin = (long)B * ((H + ws - 1) / ws) * ((W + ws - 1) / ws);
-    const int nt = wattn_ntiles(ws);
-    return (long)nH * wattn_bwd_groups((int)nwin, nH, nt) * (nt * 16) * (nt * 16);
+    const int G = wattn_bwd_groups_checked(B, H, W, nH, ws);
+    const int np = G > 0 ? wattn_ntiles(ws) * 16 : 0;
+    return (long)nH * G * np * np;
 }
 
 // dgrads: (nH * (2ws-1)^2 + 3C) fp32, overwritten: the gradient of the relative-position table as [head][(2ws-1)^2], then
