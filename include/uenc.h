@@ -313,7 +313,10 @@ long uenc_mha_fwd_workspace_floats(int B, int H, int Lq, int S);
 int uenc_mha_fwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
                  long v_rs, const unsigned char* mask, long mask_rs, void* out, long o_bs, long o_rs, float* lse,
                  float* workspace, int B, int H, int Lq, int S, float scale, float dropout_p, unsigned seed, uenc_stream_t stream);
-/* dq (B,Lq,*) fp32 ACCUMULATED (caller zeroes); dk, dv (B,S,*) bf16 overwritten for every key and head. */
+/* dq (B,Lq,*) fp32 ACCUMULATED (caller zeroes); dk, dv (B,S,*) bf16 overwritten for every key and head.
+ * Lq <= 960 without a mask and <= 640 with one: the dK / dV kernel keeps all queries in LDS, slices = ceil(Lq / 160),
+ * slices * 160 * 136 + 16384 (+ 64 * (slices * 160 + 4) with a mask) <= 160 KB.  A longer Lq returns UENC_EINVAL before anything is
+ * launched (dq included). */
 int uenc_mha_bwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
                  long v_rs, const unsigned char* mask, long mask_rs, const void* out, long o_bs, long o_rs,
                  const float* lse, const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk,

@@ -583,10 +583,12 @@ static int mha_bwd_impl(const void* q, long q_bs, long q_rs, const void* k, long
     p.dq = dq; p.dq_bs = dq_bs; p.dq_rs = dq_rs;
     p.dk = (bf16*)dk; p.dk_bs = dk_bs; p.dk_rs = dk_rs; p.dv = (bf16*)dv; p.dv_bs = dv_bs; p.dv_rs = dv_rs;
     const int slices = (Lq + MQ - 1) / MQ;
-    if (p.drop_thresh != 0u) hipLaunchKernelGGL((mha_q_kernel<1, true>), dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16), 1, slices), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((mha_q_kernel<1, false>), dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16), 1, slices), dim3(256), 0, stream, p);
+    // the dK / dV kernel holds Q, dO, lse, delta (and the mask tile) of ALL queries in LDS: Lq <= 960, <= 640 with a mask.  Refused before
+    // the dQ launch, which accumulates into the caller's dq
     const size_t shm = (size_t)slices * MQ * 64 * 2 + 4 * KB * 64 + (size_t)slices * MQ * 8 + (mask != nullptr ? (size_t)KB * (slices * MQ + 4) : 0);
     if (shm > 160 * 1024) return UENC_EINVAL;
+    if (p.drop_thresh != 0u) hipLaunchKernelGGL((mha_q_kernel<1, true>), dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16), 1, slices), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((mha_q_kernel<1, false>), dim3((unsigned)((p.nsplit * B * H + 15) / 16 * 16), 1, slices), dim3(256), 0, stream, p);
     const bool drop = p.drop_thresh != 0u;
     if (shm > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(drop ? (const void*)mha_dkdv_kernel<true> : (const void*)mha_dkdv_kernel<false>,
