@@ -128,7 +128,17 @@ int uenc_col2im3x3_s2(const void* dcol, float* dx, int B, int H, int W, int C, u
 int uenc_gemm_nt(const void* A, int a_dtype, long lda, const void* W, long ldw, void* C, int c_dtype, long ldc,
                  int M, int N, int K, const float* bias, int epilogue, const void* aux, long ldaux,
                  void* aux_out, long ldaux_out, float alpha, int splitk, int accumulate, uenc_stream_t stream);
-/* The same with alpha multiplied per SAMPLE: row m uses alpha * sample_scale[m / rows_per_sample] (sample_scale: device fp32).
+/* The same on the large-tile kernel the caller names instead of the one the library's measured rules would pick (tile = 0: exactly
+ * uenc_gemm_nt).  For tests and A/B measurements.  The tile replaces the choice only: where the shape is not one that kernel takes
+ * (bf16 A, N >= 192, N % 8 == 0, K >= 128, K % 64 == 0 -- K % 32 == 0 for 128 x 256 --, at least 160 tiles of 256 x 256; no split-K /
+ * accumulate on the 256 x 192 and 128 x 256 tiles) the call returns -1 and launches nothing. */
+#define UENC_NT_TILE_256X256 256
+#define UENC_NT_TILE_256X192 192
+#define UENC_NT_TILE_128X256 128
+int uenc_gemm_nt_tile(const void* A, int a_dtype, long lda, const void* W, long ldw, void* C, int c_dtype, long ldc,
+                      int M, int N, int K, const float* bias, int epilogue, const void* aux, long ldaux,
+                      void* aux_out, long ldaux_out, float alpha, int splitk, int accumulate, int tile, uenc_stream_t stream);
+/* uenc_gemm_nt with alpha multiplied per SAMPLE: row m uses alpha * sample_scale[m / rows_per_sample] (sample_scale: device fp32).
  * Stochastic depth as an epilogue -- timm DropPath(x) = x * floor(keep + U) / keep per image (reference backbone/swin.py:8, 279, 289):
  * the residual-branch GEMM runs over all images at once, a dropped image's rows come out as the residual alone.  Stored results only. */
 int uenc_gemm_nt_scaled(const void* A, int a_dtype, long lda, const void* W, long ldw, void* C, int c_dtype, long ldc,
@@ -161,6 +171,10 @@ int uenc_gemm_nt_batched(const void* A, int a_dtype, long lda, long bsA, const v
  * mm / sum backward of every Linear above. */
 int uenc_gemm_tn(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,
                  float* db, int M, int N, int K, int splitm, uenc_stream_t stream);
+/* The same on the LDS-DMA kernel with the output tile the caller names (tile = 256 or 128; 0: exactly uenc_gemm_tn).  For tests.
+ * Returns -1 and launches nothing unless both operands are bf16, M % 64 == 0 and M >= 2048. */
+int uenc_gemm_tn_tile(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,
+                      float* db, int M, int N, int K, int splitm, int tile, uenc_stream_t stream);
 /* dW += alpha * dY^T X, db += alpha * column sums: the weight gradient of a residual branch whose output was scaled by alpha
  * (stochastic depth, timm DropPath at reference backbone/swin.py:279, 289; the branch's dropped images are left out of M). */
 int uenc_gemm_tn_scaled(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,

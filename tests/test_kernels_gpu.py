@@ -330,7 +330,7 @@ def test_gemm_nt_large_tile_path(K, M, N, K_):
 
 
 @pytest.mark.parametrize("M,N,K_", [(40008, 520, 128), (41000, 776, 320), (45000, 200, 192), (16384, 768, 768), (66000, 384, 64 * 7)])
-def test_gemm_nt_192_wide_tile(K, M, N, K_, monkeypatch):
+def test_gemm_nt_192_wide_tile(K, M, N, K_):
     """The 256 x 192 tile of the persistent LDS-DMA kernel (three 16-MFMA phases per k-tile, an unpaired third column group per wave) forced on
     ragged shapes -- last column tile 136 / 8 / 192 wide, 2 ... 12 k-tiles, persistent and one-tile-per-workgroup grids -- against the
     256-wide tile (bit-identical: same k order) and against fp32 matmul, every epilogue."""
@@ -341,23 +341,21 @@ def test_gemm_nt_192_wide_tile(K, M, N, K_, monkeypatch):
     saved = _r(M, N, seed=5, dtype=torch.bfloat16)
     pre = a.float() @ w.float().t() + bias
 
-    def run_all():
-        outs = [K.gemm_nt(a, w, bias=bias, out_dtype=torch.float32), K.gemm_nt(a, w, bias=bias)]
+    def run_all(tile):
+        outs = [K.gemm_nt(a, w, bias=bias, out_dtype=torch.float32, tile=tile), K.gemm_nt(a, w, bias=bias, tile=tile)]
         po = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
-        outs += [K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_GELU, aux_out=po), po]
-        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU))
-        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.float32))
-        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.bfloat16))
-        outs.append(K.gemm_nt(a, w, epilogue=K.EPI_MUL_DGELU, aux=saved))
-        outs.append(K.gemm_nt(a, w, epilogue=K.EPI_MUL_DRELU, aux=saved))
-        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU, out_dtype=torch.float32))
+        outs += [K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_GELU, aux_out=po, tile=tile), po]
+        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU, tile=tile))
+        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.float32, tile=tile))
+        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.bfloat16, tile=tile))
+        outs.append(K.gemm_nt(a, w, epilogue=K.EPI_MUL_DGELU, aux=saved, tile=tile))
+        outs.append(K.gemm_nt(a, w, epilogue=K.EPI_MUL_DRELU, aux=saved, tile=tile))
+        outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU, out_dtype=torch.float32, tile=tile))
         torch.cuda.synchronize()
         return outs
 
-    monkeypatch.setenv("UENC_GEMM_VARIANT", str(262144 | 8388608))
-    wide = run_all()
-    monkeypatch.setenv("UENC_GEMM_VARIANT", str(262144 | 4194304))
-    narrow = run_all()
+    wide = run_all(K.NT_TILE_256X256)
+    narrow = run_all(K.NT_TILE_256X192)
     for x, y in zip(wide, narrow):
         assert torch.equal(x, y)
     _close(narrow[0], pre, 2e-3, 2e-3)
@@ -369,8 +367,8 @@ def test_gemm_nt_192_wide_tile(K, M, N, K_, monkeypatch):
     _close(narrow[8], (pre - bias) * (saved.float() > 0), 3e-2, 2e-2)
     ai = (torch.arange(M * K_, dtype=torch.float32).reshape(M, K_) % 7 - 3).to(torch.bfloat16).cuda()
     wi = (torch.arange(N * K_, dtype=torch.float32).reshape(N, K_) % 5 - 2).to(torch.bfloat16).cuda()
-    _close(K.gemm_nt(ai, wi, out_dtype=torch.float32), ai.float() @ wi.float().t(), 0, 0)
-    _close(K.gemm_nt(ai, wi).float(), (ai.float() @ wi.float().t()).to(torch.bfloat16).float(), 0, 0)
+    _close(K.gemm_nt(ai, wi, out_dtype=torch.float32, tile=K.NT_TILE_256X192), ai.float() @ wi.float().t(), 0, 0)
+    _close(K.gemm_nt(ai, wi, tile=K.NT_TILE_256X192).float(), (ai.float() @ wi.float().t()).to(torch.bfloat16).float(), 0, 0)
 
 
 @pytest.mark.parametrize("M,N,K_,split", [(150, 256, 32768, 64), (600, 512, 8192, 16), (1000, 256, 4096 + 64, 16)])
@@ -388,19 +386,18 @@ def test_gemm_nt_splitk_large_tile(K, M, N, K_, split):
     _close(acc, acc0 + want - bias, 2e-3 * float(want.abs().max()), 2e-3)
 
 
-@pytest.mark.parametrize("variant", ["0", "8"])
+@pytest.mark.parametrize("tile", [0, 256])
 @pytest.mark.parametrize("M,N,K_", [(4096, 512, 256), (2048, 576, 192), (8192, 768, 3072), (6400, 264, 200), (2048, 96, 48)])
-def test_gemm_tn_large_tile_path(K, M, N, K_, variant, monkeypatch):
+def test_gemm_tn_large_tile_path(K, M, N, K_, tile):
     """wgrad shapes through the LDS-DMA + transposed-read kernels: production dispatch (128x128 tiles for small
     outputs, 256x256 from 20 tiles up) and the 256x256 kernel forced; ragged N / K tiles and db."""
-    monkeypatch.setenv("UENC_GEMM_VARIANT", variant)
     dy = _r(M, N, seed=1, dtype=torch.bfloat16)
     x = _r(M, K_, seed=2, dtype=torch.bfloat16)
     dw = _r(N, K_, seed=3)
     db = _r(N, seed=4)
     want_w = dw + dy.float().t() @ x.float()
     want_b = db + dy.float().sum(0)
-    K.gemm_tn(dy, x, dw, db)
+    K.gemm_tn(dy, x, dw, db, tile=tile)
     tol = 4e-3 * (M ** 0.5)
     _close(dw, want_w, tol, 2e-3)
     _close(db, want_b, tol, 2e-3)
@@ -408,8 +405,117 @@ def test_gemm_tn_large_tile_path(K, M, N, K_, variant, monkeypatch):
     dyi = (torch.arange(M * N, dtype=torch.float32).reshape(M, N) % 5 - 2).to(torch.bfloat16).cuda()
     xi = (torch.arange(M * K_, dtype=torch.float32).reshape(M, K_) % 3 - 1).to(torch.bfloat16).cuda()
     dwi = torch.zeros(N, K_, device="cuda")
-    K.gemm_tn(dyi, xi, dwi, None, splitm=1)
+    K.gemm_tn(dyi, xi, dwi, None, splitm=1, tile=tile)
     _close(dwi, dyi.float().t() @ xi.float(), 0, 0)
+
+
+_RETIRED_GEMM_BITS = (2, 4, 8, 16, 64, 128, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 524288, 1048576, 2097152,
+                      4194304, 8388608, 33554432)
+
+
+def _gemm_prof(kind):
+    """(launches, algorithmic bytes) the launch timers recorded for one kind since uenc_prof_enable(1): 0 the register-staged 128 x 128
+    and the skinny NT kernels, 1 every TN kernel, 4 the 256 x 256 / 256 x 192 NT kernel, 5 the 128 x 256 one.  Call after a synchronise."""
+    import ctypes
+    from uenc.capi import lib
+    n, by = ctypes.c_long(), ctypes.c_double()
+    lib.uenc_prof_collect(kind, None, None, ctypes.byref(n))
+    lib.uenc_prof_collect_bytes(kind, ctypes.byref(by))
+    return n.value, by.value
+
+
+def test_gemm_ignores_retired_switch(K, monkeypatch):
+    """UENC_GEMM_VARIANT (a mask of about 25 A/B bits: dispatch terms, main loops, epilogue forms, a timing experiment that dropped the
+    epilogue altogether) is no longer read: with every former bit set, each kernel's results are bit-identical to the run without the
+    variable.  One small shape per route, a bf16 output and an fp32 residual output each.  Written for the 256-CU device: the choice
+    between the 256 x 192 and the 256 x 256 tile counts rounds of tiles over the CUs.  The kernel family of each NT shape is checked
+    through the launch timers' kinds; (1000, 136, 72) is 16 tiles of 128 x 128 and goes to the skinny kernel like (300, 256, 256), so
+    (5000, 136, 72) is there for the register-staged 128 x 128 kernel.  The TN cases run one token split: no two workgroups add into
+    one element."""
+    from uenc.capi import lib
+    nt = [((300, 256, 256), 0), ((1000, 136, 72), 0), ((5000, 136, 72), 0), ((12288, 256, 128), 5), ((20480, 320, 128), 4), ((20480, 768, 128), 4)]
+    tn = [(2048, 96, 48), (2048, 1032, 1000)]
+    ops = []
+    for (M, N, K_), _ in nt:
+        a = _r(M, K_, seed=1, dtype=torch.bfloat16)
+        w = _r(N, K_, seed=2, scale=K_ ** -0.5, dtype=torch.bfloat16)
+        ops.append((a, w, _r(N, seed=3), _r(M, N, seed=4)))
+    tops = [(_r(M, N, seed=1, dtype=torch.bfloat16), _r(M, K_, seed=2, dtype=torch.bfloat16)) for M, N, K_ in tn]
+
+    def run():
+        outs = []
+        for a, w, bias, res in ops:
+            outs.append(K.gemm_nt(a, w, bias=bias))
+            outs.append(K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.float32))
+        for dy, x in tops:
+            dw = torch.zeros(dy.shape[1], x.shape[1], device="cuda")
+            db = torch.zeros(dy.shape[1], device="cuda")
+            K.gemm_tn(dy, x, dw, db, splitm=1)
+            outs += [dw, db]
+        torch.cuda.synchronize()
+        return outs
+
+    monkeypatch.delenv("UENC_GEMM_VARIANT", raising=False)
+    lib.uenc_prof_enable(1)
+    try:
+        base = run()
+        launches = {k: _gemm_prof(k)[0] for k in (0, 1, 4, 5)}
+    finally:
+        lib.uenc_prof_enable(0)
+    assert launches == {0: 6, 1: len(tn), 4: 4, 5: 2}
+    for (a, w, bias, res), o16, o32 in zip(ops, base[0::2], base[1::2]):
+        pre = a.float() @ w.float().t() + bias
+        _close(o16, pre, 2e-2, 1e-2)
+        _close(o32, pre + res, 2e-3, 2e-3)
+    for (dy, x), dw, db in zip(tops, base[2 * len(nt)::2], base[2 * len(nt) + 1::2]):
+        _close(dw, dy.float().t() @ x.float(), 4e-3 * dy.shape[0] ** 0.5, 2e-3)
+        _close(db, dy.float().sum(0), 4e-3 * dy.shape[0] ** 0.5, 2e-3)
+    monkeypatch.setenv("UENC_GEMM_VARIANT", str(sum(_RETIRED_GEMM_BITS)))
+    got = run()
+    assert len(got) == len(base) == 2 * len(nt) + 2 * len(tn)
+    for i, (x, y) in enumerate(zip(got, base)):
+        assert torch.equal(x, y), i
+
+
+def test_gemm_tile_refused_when_not_legal(K):
+    """`tile` replaces the measured choice between kernels, never a legality condition: a shape the named kernel does not take is an
+    error and nothing is launched (the output keeps its sentinel)."""
+    from uenc.capi import UencError
+    a = _r(300, 256, seed=1, dtype=torch.bfloat16)
+    w = _r(256, 256, seed=2, scale=1 / 16, dtype=torch.bfloat16)
+    for dtype in (torch.bfloat16, torch.float32):
+        out = torch.full((300, 256), 7.0, dtype=dtype, device="cuda")
+        with pytest.raises(UencError):
+            K.gemm_nt(a, w, out=out, tile=K.NT_TILE_256X192)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all())
+    dy = _r(1000, 64, seed=3, dtype=torch.bfloat16)
+    x = _r(1000, 40, seed=4, dtype=torch.bfloat16)
+    dw = torch.full((64, 40), 7.0, device="cuda")
+    db = torch.full((64,), 7.0, device="cuda")
+    with pytest.raises(UencError):
+        K.gemm_tn(dy, x, dw, db, tile=256)
+    torch.cuda.synchronize()
+    assert bool((dw == 7.0).all()) and bool((db == 7.0).all())
+
+
+def test_gemm_nt_ln_refusal_leaves_no_profiling_record(K, monkeypatch):
+    """A fused-LayerNorm call on a shape the LDS-staged kernels do not take is refused before a launch-timer record is opened: the
+    timers hold no launch and no bytes for it (the record used to be opened and never closed: its bytes counted, its end event never
+    recorded)."""
+    from uenc.capi import lib
+    monkeypatch.delenv("UENC_GEMM_LN", raising=False)
+    M, N, K_ = 300, 256, 256
+    a = _r(M, K_, seed=1, dtype=torch.bfloat16)
+    w = _r(N, K_, seed=2, scale=K_ ** -0.5, dtype=torch.bfloat16)
+    lib.uenc_prof_enable(1)
+    try:
+        assert K.gemm_nt_ln(a, w, _r(N, seed=3), _r(M, N, seed=4), 1 + 0.1 * _r(N, seed=5), _r(N, seed=6)) is None
+        torch.cuda.synchronize()
+        for kind in (0, 4, 5):
+            assert _gemm_prof(kind) == (0, 0.0), kind
+    finally:
+        lib.uenc_prof_enable(0)
 
 
 @pytest.mark.parametrize("shape,size", [((2, 5, 16, 24), (64, 96)), ((1, 3, 7, 9), (28, 36)), ((1, 2, 10, 6), (17, 20))])

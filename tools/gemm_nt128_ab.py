@@ -1,5 +1,6 @@
-"""A/B of the two large-tile NT kernels per workload shape: gemm_nt256 (one workgroup per CU, UENC_GEMM_VARIANT bit 262144) vs gemm_nt128 (two per CU,
-bit 131072): results must be bit-identical (same k order), times per epilogue.  GPU box."""
+"""A/B of the two large-tile NT kernels per workload shape: gemm_nt256 (one workgroup per CU, tile=K.NT_TILE_256X256) vs gemm_nt128 (two per CU,
+tile=K.NT_TILE_128X256): results must be bit-identical (same k order), times per epilogue.  A shape the large-tile kernels do not take (fewer
+than 160 tiles of 256 x 256) is refused by the library and listed as such.  GPU box."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uni-encoder-code_amd"))
 from uenc import kernels as K
@@ -35,24 +36,26 @@ for M, N, Kd, tag, epis in shapes:
     res = torch.randn(M, N, device="cuda", generator=g)
     pre = torch.randn(M, N, device="cuda", generator=g).to(torch.bfloat16)
     for e in epis:
-        def run():
-            if e == "none": return (K.gemm_nt(a, w, bias=bias, out_dtype=torch.bfloat16),)
-            if e == "nonef32": return (K.gemm_nt(a, w, bias=bias, out_dtype=torch.float32),)
-            if e == "res": return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.float32),)
-            if e == "relu": return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU),)
+        def run(tile):
+            if e == "none": return (K.gemm_nt(a, w, bias=bias, out_dtype=torch.bfloat16, tile=tile),)
+            if e == "nonef32": return (K.gemm_nt(a, w, bias=bias, out_dtype=torch.float32, tile=tile),)
+            if e == "res": return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RESIDUAL, aux=res, out_dtype=torch.float32, tile=tile),)
+            if e == "relu": return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_RELU, tile=tile),)
             if e == "gelu":
                 po = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-                return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_GELU, aux_out=po), po)
-            if e == "dgelu": return (K.gemm_nt(a, w, epilogue=K.EPI_MUL_DGELU, aux=pre),)
-            if e == "drelu": return (K.gemm_nt(a, w, epilogue=K.EPI_MUL_DRELU, aux=pre),)
+                return (K.gemm_nt(a, w, bias=bias, epilogue=K.EPI_GELU, aux_out=po, tile=tile), po)
+            if e == "dgelu": return (K.gemm_nt(a, w, epilogue=K.EPI_MUL_DGELU, aux=pre, tile=tile),)
+            if e == "drelu": return (K.gemm_nt(a, w, epilogue=K.EPI_MUL_DRELU, aux=pre, tile=tile),)
         outs, times = {}, {}
-        for name, v in (("nt256", 262144), ("nt128", 131072)):
-            os.environ["UENC_GEMM_VARIANT"] = str(v)
-            outs[name] = [o.clone() for o in run()]
-            times[name] = timeit(run)
+        try:
+            for name, tile in (("nt256", K.NT_TILE_256X256), ("nt128", K.NT_TILE_128X256)):
+                outs[name] = [o.clone() for o in run(tile)]
+                times[name] = timeit(lambda: run(tile))
+        except K.capi.UencError:
+            print(f"{tag:10s} {M:7d}x{N:5d}x{Kd:5d}   {e:>9s}  not a large-tile shape: refused", flush=True)
+            continue
         same = all(torch.equal(x, y) for x, y in zip(outs["nt256"], outs["nt128"]))
         ok &= same
         print(f"{tag:10s} {M:7d}x{N:5d}x{Kd:5d}   {e:>9s} {times['nt256']:9.1f} {times['nt128']:9.1f} {times['nt128'] / times['nt256']:6.2f}  {same}", flush=True)
-    os.environ["UENC_GEMM_VARIANT"] = "0"
     del a, w, res, pre
 print("ALL IDENTICAL" if ok else "MISMATCH")

@@ -1,8 +1,8 @@
 """Race screen of the 256-tile NT kernel: every shape is run `reps` times on fresh random operands while another stream keeps the
 memory system busy; each result must equal the fp32 product of the same bf16 operands (to accumulation order) and be bit-identical
-between repeats of the same operands.  UENC_GEMM_VARIANT selects the main loop under test."""
+between repeats of the same operands."""
 import os, sys, torch
-sys.path.insert(0, '/root/repo/uni-encoder-code_amd')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uni-encoder-code_amd"))
 from uenc import kernels as K
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 6
@@ -30,5 +30,5 @@ for M, N, Kd in shapes:
             print(f"BAD {M}x{N}x{Kd} rep {r}: rel-max err {err:.3e} identical {same}", flush=True)
     print(f"{M}x{N}x{Kd} ok", flush=True)
 torch.cuda.synchronize()
-print("race screen:", "FAILED %d" % bad if bad else "clean", f"({len(shapes)} shapes x {reps} reps, variant {os.environ.get('UENC_GEMM_VARIANT', '0')})")
+print("race screen:", "FAILED %d" % bad if bad else "clean", f"({len(shapes)} shapes x {reps} reps)")
 sys.exit(1 if bad else 0)

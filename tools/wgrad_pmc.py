@@ -1,12 +1,11 @@
 """A few grouped-wgrad launches of one problem set for rocprofv3 --pmc passes (FETCH_SIZE: L2 <-> fabric read traffic).
-usage: wgrad_pmc.py <UENC_GEMM_VARIANT> [set]    set: s3 (default) | s1 | s4"""
+usage: wgrad_pmc.py [set]    set: s3 (default) | s1 | s4"""
 import os, sys, torch
-os.environ["UENC_GEMM_VARIANT"] = sys.argv[1] if len(sys.argv) > 1 else "0"
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uni-encoder-code_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from uenc.ops import WgradQueue
 import importlib.util
-which = sys.argv[2] if len(sys.argv) > 2 else "s3"
+which = sys.argv[1] if len(sys.argv) > 1 else "s3"
 M, C, layers = {"s3": (16384, 768, 6), "s1": (262144, 192, 2), "s4": (4096, 1536, 2)}[which]
 probs = []
 for _ in range(layers):

@@ -18,7 +18,6 @@
 // and conflict-free ds_write_b128 staging.
 #include "common.h"
 #include "prof.h"
-#include <stdlib.h>
 
 #define BM 128
 #define BN 128
@@ -38,7 +37,6 @@ struct GemmNT {
     int tiles_m, tiles_n;
     int klen;      // K elements handled by one split (multiple of BK); == K rounded up when splitk == 1
     int atomic;    // fp32 atomicAdd into C (split-K or accumulate)
-    int variant;   // debug A/B switch
     int persist;   // gemm_nt256_kernel: the grid is smaller than the tile count, workgroups walk tile positions
     float alpha;
     const float* sample_scale; float inv_rows;   // optional per-sample multiplier of alpha: row m belongs to sample floor(m / rows_per_sample)
@@ -258,7 +256,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_nt_kernel(GemmNT p) {
 
 
 // ---------------------------------------------------------------------------------------------
-// Skinny variant for the GEMMs with a handful of output tiles (the transformer decoder: M = B * 150 query rows, N = 256 ... 2048,
+// Skinny kernel for the GEMMs with a handful of output tiles (the transformer decoder: M = B * 150 query rows, N = 256 ... 2048,
 // K up to 2048; ~250 launches per step that ran 6 ... 48 workgroups of the 128-tile kernel for 10 ... 25 us each, every k-tile
 // paying a full memory latency).  Here a workgroup owns a 64 x 64 tile and its four waves split the K range between them:
 // fragments go global -> registers directly in MFMA layout (nothing is shared between waves, so no LDS staging), 4 k-steps
@@ -398,18 +396,15 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(GemmNT p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Large-tile variant for the GEMMs that carry most of the FLOPs (stage 3 / 4 of the backbone,
+// Large-tile kernel for the GEMMs that carry most of the FLOPs (stage 3 / 4 of the backbone,
 // K % 64 == 0, bf16 A): 256 x 256 x 64 tile, 8 waves (2 x 4), each wave 128(m) x 64(n) = 8 x 4
 // MFMA tiles (128 accumulator VGPRs), one workgroup per CU.  Operands go global -> LDS directly
 // (global_load_lds_dwordx4: no staging registers).  LDS-DMA writes lane-linearly (wave base +
 // lane * 16 B), so the XOR swizzle that keeps the ds_read_b128 fragment reads conflict-free is
 // applied to the per-lane SOURCE address (cdna_hip_programming.md rule 21).
-// Main loop PIPE = 1 (default): the staggered quadrant pipeline described in the kernel (half-tile
-// DMA stream six half-tiles ahead, counted vmcnt, raw s_barrier, the two waves of a SIMD one
-// barrier apart): 1.30 PFLOP/s at 8192^3 on random operands, +3...14 % over PIPE = 0 on the
-// workload's shapes.  PIPE = 0: two 64 KB stages, the DMA of k-tile t+1 issued before the 64
-// MFMAs per wave of k-tile t and drained by the __syncthreads() after them (kept for A/B:
-// UENC_GEMM_VARIANT bit 128).
+// Main loop: the staggered quadrant pipeline described in the kernel (half-tile DMA stream six
+// half-tiles ahead, counted vmcnt, raw s_barrier, the two waves of a SIMD one barrier apart):
+// 1.30 PFLOP/s at 8192^3 on random operands.
 // ---------------------------------------------------------------------------------------------
 #define BM2 256
 #define BN2 256
@@ -437,8 +432,7 @@ __device__ __forceinline__ void wait_vmcnt_upto8(int n) {
 // activation of the dGELU / dReLU epilogues is read the same way.  No LDS, no barriers: the LDS-staged form below takes 6 us
 // of a 27 us K = 768 tile (four passes, eight barriers, half the waves idle in each); measured on the workload's shapes the
 // direct form is 5-13 % faster per launch for bf16 results.  fp32 results keep the staged form: its 1 KB runs per row beat
-// 64-byte (direct) and 256-byte (per-wave patches) runs by 7-20 % on the HBM-bound shapes.  Bit 32768 of UENC_GEMM_VARIANT
-// selects the staged form everywhere (A/B).
+// 64-byte (direct) and 256-byte (per-wave patches) runs by 7-20 % on the HBM-bound shapes.
 // NI = column groups of 16 the wave owns (4: the 64-wide patch; 3: the 48-wide patch of the 256 x 192 tile -- its third group has no
 // partner to trade halves with and moves as 8-byte pieces: a third of the tile's bytes in 32-byte runs).
 template <int EPI, int NI = 4>
@@ -463,9 +457,8 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
     // operations retire in order, and the compiler may not move these loads above the stores (C and aux may alias as far as it knows):
     // inside the row loop every row's load waited behind the previous row's stores -- eight load -> store round trips per tile,
     // 64 us of a 124 us N = 3072 dGELU launch against 32 us for the same bytes streamed.  Four rows per batch = two round trips;
-    // all eight at once spilled (bit 1048576 of UENC_GEMM_VARIANT restores the per-row loads, A/B).
+    // all eight at once spilled.
     constexpr bool AUX16 = (EPI == EPI_MUL_DGELU || EPI == EPI_MUL_DRELU);
-    const bool hoist = !(p.variant & 1048576);
     u32x4 xa[AUX16 ? 4 : 1][2];                         // saved bf16 activation: four rows at a time (32 registers)
     u32x2 xo[AUX16 && ODD ? 4 : 1];                     // ... of the unpaired group
     float4 ra[EPI == EPI_RESIDUAL ? 2 : 1][4];          // fp32 residual: two rows at a time (32 registers)
@@ -473,22 +466,20 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
     for (int j = 0; j < 8; ++j) {
         const int m = mrow + j * 16;
         const bool row_ok = m < p.M;
-        if (AUX16 && hoist && (j & 3) == 0) {
+        if (AUX16 && (j & 3) == 0) {
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 const int mm = mrow + (j + jj) * 16;
 #pragma unroll
-                for (int pr = 0; pr < NP; ++pr) {
-                    xa[jj][pr] = (u32x4){0u, 0u, 0u, 0u};
-                    if (mm < p.M && n16[pr] < p.N) xa[jj][pr] = *(const u32x4*)((const bf16*)p.aux + (long)mm * p.ldaux + n16[pr]);
-                }
-                if (ODD) {
-                    xo[AUX16 && ODD ? jj : 0] = (u32x2){0u, 0u};
-                    if (mm < p.M && nodd < p.N) xo[AUX16 && ODD ? jj : 0] = *(const u32x2*)((const bf16*)p.aux + (long)mm * p.ldaux + nodd);
-                }
+                // branch-free, the address clamped into the matrix (N % 8 == 0 here): written as `zero, then load if inside` every load was
+                // followed by its own vmcnt(0) -- eight round trips per batch, 6-14 % of a dGELU / dReLU launch.  What a lane reads for a row
+                // or column group past the edge only ever reaches results of that row / group, which are not stored.
+                for (int pr = 0; pr < NP; ++pr)
+                    xa[jj][pr] = *(const u32x4*)((const bf16*)p.aux + (long)min(mm, p.M - 1) * p.ldaux + min(n16[pr], p.N - 8));
+                if (ODD) xo[AUX16 && ODD ? jj : 0] = *(const u32x2*)((const bf16*)p.aux + (long)min(mm, p.M - 1) * p.ldaux + min(nodd, p.N - 4));
             }
         }
-        if (EPI == EPI_RESIDUAL && hoist && (j & 1) == 0) {
+        if (EPI == EPI_RESIDUAL && (j & 1) == 0) {
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
@@ -521,23 +512,15 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
         } else if (EPI == EPI_RESIDUAL) {
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
-                const int n = ncol + i * 16;
-                if (hoist) {
-                    const float4 r0 = ra[j & 1][i];
-                    v[i][0] += r0.x; v[i][1] += r0.y; v[i][2] += r0.z; v[i][3] += r0.w;
-                } else if (row_ok && n < p.N) {
-                    const float4 r0 = *(const float4*)((const float*)p.aux + (long)m * p.ldaux + n);
-                    v[i][0] += r0.x; v[i][1] += r0.y; v[i][2] += r0.z; v[i][3] += r0.w;
-                }
+                const float4 r0 = ra[j & 1][i];
+                v[i][0] += r0.x; v[i][1] += r0.y; v[i][2] += r0.z; v[i][3] += r0.w;
             }
         } else if (EPI == EPI_MUL_DGELU || EPI == EPI_MUL_DRELU) {
             // the saved bf16 activation is read in the widened layout (16 bytes per lane) and brought back to the accumulator
             // layout by the same swap (an involution)
 #pragma unroll
             for (int pr = 0; pr < NP; ++pr) {
-                u32x4 x = {0u, 0u, 0u, 0u};
-                if (hoist) x = xa[AUX16 ? (j & 3) : 0][pr];
-                else if (row_ok && n16[pr] < p.N) x = *(const u32x4*)((const bf16*)p.aux + (long)m * p.ldaux + n16[pr]);
+                const u32x4 x = xa[AUX16 ? (j & 3) : 0][pr];
                 const u32x2 lo = __builtin_amdgcn_permlane16_swap(x[0], x[2], false, false);
                 const u32x2 hi = __builtin_amdgcn_permlane16_swap(x[1], x[3], false, false);
                 const u32x2 sa = {lo[0], hi[0]}, sb = {lo[1], hi[1]};
@@ -549,9 +532,7 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
                 }
             }
             if (ODD) {                                  // the unpaired group: already in the accumulator layout
-                u32x2 x = {0u, 0u};
-                if (hoist) x = xo[AUX16 && ODD ? (j & 3) : 0];
-                else if (row_ok && nodd < p.N) x = *(const u32x2*)((const bf16*)p.aux + (long)m * p.ldaux + nodd);
+                const u32x2 x = xo[AUX16 && ODD ? (j & 3) : 0];
                 const bf16x4 s0 = *(const bf16x4*)&x;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -574,8 +555,7 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
                 const u32x2 hi = __builtin_amdgcn_permlane16_swap(o2[2 * pr][1], o2[2 * pr + 1][1], false, false);
                 if (row_ok && n16[pr] < p.N) {
                     const u32x4 o4 = {lo[0], hi[0], lo[1], hi[1]};
-                    if (p.variant & 524288) __builtin_nontemporal_store(o4, (u32x4*)((bf16*)p.C + (long)m * p.ldc + n16[pr]));      // A/B: streaming stores
-                    else *(u32x4*)((bf16*)p.C + (long)m * p.ldc + n16[pr]) = o4;
+                    *(u32x4*)((bf16*)p.C + (long)m * p.ldc + n16[pr]) = o4;
                 }
             }
         }
@@ -587,26 +567,25 @@ __device__ __forceinline__ void nt_epilogue_direct(const GemmNT& p, f32x4 (&acc)
                 const u32x2 hi = __builtin_amdgcn_permlane16_swap(pre2[2 * pr][1], pre2[2 * pr + 1][1], false, false);
                 if (row_ok && n16[pr] < p.N) {
                     const u32x4 o4 = {lo[0], hi[0], lo[1], hi[1]};
-                    if (p.variant & 524288) __builtin_nontemporal_store(o4, (u32x4*)(p.aux_out + (long)m * p.ldaux_out + n16[pr]));
-                    else *(u32x4*)(p.aux_out + (long)m * p.ldaux_out + n16[pr]) = o4;
+                    *(u32x4*)(p.aux_out + (long)m * p.ldaux_out + n16[pr]) = o4;
                 }
             }
         }
     }
 }
 
-// ---- LDS-staged epilogue (fp32 results; bf16 under UENC_GEMM_VARIANT bit 32768): passes of 64 rows through a padded fp32 tile [64][260]
+// ---- LDS-staged epilogue (fp32 results): passes of 64 rows through a padded fp32 tile [64][260]
 // in LDS, then 8 consecutive columns per thread: 1 KB runs per row.  NWM = row groups of 128 the workgroup owns (wave group wm each). ----
 // NI = column groups of 16 per wave (4, or 3 for the 192-wide tile: the tile then spans 4 x 48 columns and the threads of the last 64 idle).
 template <int EPI, int OUT_F32, int NTHREADS, int NWM, int NI = 4, bool LN = false>
 __device__ __forceinline__ void nt_epilogue_staged(const GemmNT& p, f32x4 (&acc)[4][8], unsigned char* smem, int m0, int n0, int wm, int wn,
-                                                   int t, int fr, int fg, bool lead, bool skip_stores) {
+                                                   int t, int fr, int fg, bool lead) {
     float* T = (float*)smem;
     constexpr int LDT = 260;
     const int erow = t >> 5, ecol = (t & 31) * 8;
     constexpr int RPI = NTHREADS / 32;            // rows one iteration of the workgroup covers
     constexpr int NIT = 64 / RPI;
-    const bool hoist = !(p.variant & 1048576) && !LN;       // (the fused-LayerNorm form loads its residual row by row)
+    constexpr bool hoist = !LN;               // (the fused-LayerNorm form loads its residual row by row)
     const int n = n0 + ecol;
     const bool ncol_ok = n < p.N && ecol < NI * 64;
     const bool full8 = (n + 8 <= p.N);
@@ -711,15 +690,6 @@ __device__ __forceinline__ void nt_epilogue_staged(const GemmNT& p, f32x4 (&acc)
             const float al = nt_alpha(p, m);
 #pragma unroll
             for (int r = 0; r < 4; ++r) { v[r] = (a0[r] + bv[r]) * al; v[4 + r] = (a1[r] + bv[4 + r]) * al; }
-            if (skip_stores) {
-                if (EPI == EPI_GELU) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = gelu_f(v[r]);
-                }
-#pragma unroll
-                for (int r = 0; r < 8; ++r) asm volatile("" :: "v"(v[r]));
-                continue;
-            }
             if (EPI == EPI_GELU) {
                 if (p.aux_out != nullptr) {
                     bf16x8 pre;
@@ -739,11 +709,6 @@ __device__ __forceinline__ void nt_epilogue_staged(const GemmNT& p, f32x4 (&acc)
                     const float4 r0 = rres[EPI == EPI_RESIDUAL ? (it & 3) : 0][0], r1 = rres[EPI == EPI_RESIDUAL ? (it & 3) : 0][1];
                     v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
                     v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
-                } else {
-                    const float* rp = (const float*)p.aux + (long)m * p.ldaux + n;
-                    const float4 r0 = *(const float4*)rp;
-                    v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
-                    if (full8) { const float4 r1 = *(const float4*)(rp + 4); v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w; }
                 }
             } else if (EPI == EPI_MUL_DGELU || EPI == EPI_MUL_DRELU) {
                 const bf16* ap = (const bf16*)p.aux + (long)m * p.ldaux + n;
@@ -780,13 +745,13 @@ __device__ __forceinline__ void nt_epilogue_staged(const GemmNT& p, f32x4 (&acc)
     }
 }
 
-// BNT = 192: the 256 x 192 tile (PIPE = 1 only).  A wave then owns 128 x 48 = three column groups: B0 keeps the first two, B1 is the third
+// BNT = 192: the 256 x 192 tile.  A wave then owns 128 x 48 = three column groups: B0 keeps the first two, B1 is the third
 // alone (a 64-row, 8 KB half-tile: ONE DMA instruction per thread, and quadrants of 16 / 8 / 8 / 16 MFMAs).  For the shapes whose
 // 256-wide tiling leaves CUs idle or columns empty: N = 768 at M = 16384 is 192 tiles of 256 x 256 on 256 CUs but 256 tiles of
 // 256 x 192; N = 2304 is 2.25 rounds of tiles against 3 rounds of 3/4 the work; N = 384 / 576 / 192 waste a quarter of their last column.
-template <int EPI, int OUT_F32, int PIPE, int BNT = BN2, bool LN = false>
+template <int EPI, int OUT_F32, int BNT = BN2, bool LN = false>
 __global__ __launch_bounds__(T2) void gemm_nt256_kernel(GemmNT p) {
-    static_assert(BNT == 256 || (BNT == 192 && PIPE == 1), "tile width");
+    static_assert(BNT == 256 || BNT == 192, "tile width");
     constexpr int NI = BNT / 64;          // column groups of 16 per wave
     constexpr int NB1 = NI - 2;           // ... of them in the B1 half-tile
     constexpr int BNW = BNT / 4;          // columns per wave
@@ -822,7 +787,7 @@ __global__ __launch_bounds__(T2) void gemm_nt256_kernel(GemmNT p) {
 
     typedef __attribute__((address_space(3))) void lds_void;
     const int fr = lane & 15, fg = lane >> 4;
-    if (PIPE) {
+    {
         // ---- staggered quadrant pipeline ----
         // A k-tile buffer (64 KB, two of them) holds four 16 KB HALF-tiles, 128 rows x 128 B each: A0 / A1 = the rows of every wave's
         // first / second 64 output rows, B0 / B1 = the W rows of every wave's first / second 32 output columns.  A k-tile is four
@@ -1057,7 +1022,7 @@ __global__ __launch_bounds__(T2) void gemm_nt256_kernel(GemmNT p) {
         }
         if (wm == 0) __builtin_amdgcn_s_barrier();             // group 0 waits for group 1's last phase
         prefetched = false;
-        if (has_next && !OUT_F32 && !(p.variant & 32768)) {     // the register-direct epilogue does not touch LDS: start the next tile's loads now
+        if (has_next && !OUT_F32) {     // the register-direct epilogue does not touch LDS: start the next tile's loads now
             const int tile2 = xcd_remap(pos_next, ntiles_all);
             const int mt2 = tile2 / p.tiles_n;
             set_src(mt2 * BM2, (tile2 - mt2 * p.tiles_n) * BNT);
@@ -1065,66 +1030,17 @@ __global__ __launch_bounds__(T2) void gemm_nt256_kernel(GemmNT p) {
             prologue();
             prefetched = true;
         }
-    } else {
-        // DMA geometry: instruction q of a thread fills LDS chunk index L = q * 512 + t  (row L >> 3, slot L & 7)
-        const bf16* asrc[4];
-        const bf16* wsrc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = q * 64 + (t >> 3), slot = t & 7;
-            const int chunk = slot ^ ((row >> 1) & 7);
-            asrc[q] = (const bf16*)p.A + (long)min(m0 + row, p.M - 1) * p.lda + chunk * 8 + (long)kt0 * BK;
-            wsrc[q] = p.W + (long)min(n0 + row, p.N - 1) * p.ldw + chunk * 8 + (long)kt0 * BK;
-        }
-        auto issue = [&](int kt, int stage) {
-            unsigned char* As = smem + stage * 65536;
-            unsigned char* Ws = As + 32768;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                __builtin_amdgcn_global_load_lds(asrc[q] + kt * BK, (lds_void*)(As + (q * 512 + wave * 64) * 16), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(wsrc[q] + kt * BK, (lds_void*)(Ws + (q * 512 + wave * 64) * 16), 16, 0, 0);
-            }
-        };
-
-        issue(0, 0);
-        for (int kt = 0; kt < nkt; ++kt) {
-            __syncthreads();     // waits for this wave's DMA (vmcnt 0), then everyone: tile kt landed, stage (kt+1)&1 is free
-            if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
-            const unsigned char* As = smem + (kt & 1) * 65536;
-            const unsigned char* Ws = As + 32768;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 wf[4], xf[8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wf[i] = *(const bf16x8*)(Ws + lds_off(wn * 64 + i * 16 + fr, ks * 4 + fg));
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xf[j] = *(const bf16x8*)(As + lds_off(wm * 128 + j * 16 + fr, ks * 4 + fg));
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[i][j] = mfma16(wf[i], xf[j], acc[i][j]);
-            }
-        }
-
     }
 
-    // epilogue: four passes of 64 rows through a padded fp32 LDS tile [64][260]; then 8 columns per thread
-    if (p.variant & 16384) {                 // timing experiment: no epilogue at all (keeps the accumulators alive)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(acc[i][j]));
-        if (!has_next) return;
-        pos = pos_next;
-        continue;
-    }
-    if (!OUT_F32 && !(p.variant & 32768)) {
+    // epilogue: register-direct for bf16 results; fp32 results take four passes of 64 rows through a padded fp32 LDS tile [64][260], then
+    // 8 columns per thread
+    if (!OUT_F32) {
         nt_epilogue_direct<EPI, NI>(p, acc, m0 + wm * 128, n0 + wn * BNW, fr, fg, blockIdx.y == 0);
         if (!has_next) return;
         pos = pos_next;
         continue;
     }
-    nt_epilogue_staged<EPI, OUT_F32, T2, 2, NI, LN>(p, acc, smem, m0, n0, wm, wn, t, fr, fg, blockIdx.y == 0, (p.variant & 8192) != 0);
+    nt_epilogue_staged<EPI, OUT_F32, T2, 2, NI, LN>(p, acc, smem, m0, n0, wm, wn, t, fr, fg, blockIdx.y == 0);
     if (!has_next) return;
     __syncthreads();          // the staged epilogue's last reads of the LDS tile precede the next tile's DMA writes
     pos = pos_next;
@@ -1132,7 +1048,7 @@ __global__ __launch_bounds__(T2) void gemm_nt256_kernel(GemmNT p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Half-height variant with TWO workgroups per CU: 128 x 256 x 32 tile, 4 waves (1 x 4), each wave the same 128(m) x 64(n) patch of
+// Half-height kernel with TWO workgroups per CU: 128 x 256 x 32 tile, 4 waves (1 x 4), each wave the same 128(m) x 64(n) patch of
 // 8 x 4 MFMA tiles as in the 256-tile kernel, 72 KB of LDS (ring of three 24 KB k-steps: A 128 rows + W 256 rows of 64 bytes).
 // Why: the 256-tile kernel owns its CU alone, and vector-memory operations of a wave retire in order -- a tile's result stores sit
 // in front of the next tile's operand DMA in the same queue, so a CU alternates between "MFMA" and "drain stores / wait for loads".
@@ -1219,12 +1135,12 @@ __global__ __launch_bounds__(T3, 2) void gemm_nt128_kernel(GemmNT p) {
             for (int j = 0; j < 8; ++j) acc[i][j] = mfma16(wf[i], xf[j], acc[i][j]);
         buf = buf == 2 ? 0 : buf + 1;
     }
-    if (!OUT_F32 && !(p.variant & 32768)) {
+    if (!OUT_F32) {
         nt_epilogue_direct<EPI>(p, acc, m0, n0 + wn * 64, fr, fg, true);
         return;
     }
     __syncthreads();          // the staged epilogue reuses the ring
-    nt_epilogue_staged<EPI, OUT_F32, T3, 1, 4, LN>(p, acc, smem, m0, n0, 0, wn, t, fr, fg, true, false);
+    nt_epilogue_staged<EPI, OUT_F32, T3, 1, 4, LN>(p, acc, smem, m0, n0, 0, wn, t, fr, fg, true);
 }
 
 template <int EPI, int OUT_F32, bool LN = false>
@@ -1251,20 +1167,37 @@ static int nt_cu_count() {
     return ncu;
 }
 
-template <int EPI, int OUT_F32, int PIPE, int BNT = BN2, bool LN = false>
+template <int EPI, int OUT_F32, int BNT = BN2, bool LN = false>
 static int launch_nt256(GemmNT& p, hipStream_t stream) {
     p.tiles_m = (p.M + BM2 - 1) / BM2; p.tiles_n = (p.N + BNT - 1) / BNT;
     static bool attr_set = false;      // per instantiation
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt256_kernel<EPI, OUT_F32, PIPE, BNT, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt256_kernel<EPI, OUT_F32, BNT, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    // more tiles than CUs: one persistent workgroup per CU walks its tile positions (bit 65536 of UENC_GEMM_VARIANT: one workgroup per tile)
+    // more tiles than CUs: one persistent workgroup per CU walks its tile positions
     const int ncu = nt_cu_count();
     const int ntiles = p.tiles_m * p.tiles_n;
-    p.persist = (PIPE == 1 && p.splits == 1 && ntiles > ncu && !(p.variant & 65536)) ? 1 : 0;
-    hipLaunchKernelGGL((gemm_nt256_kernel<EPI, OUT_F32, PIPE, BNT, LN>), dim3(p.persist ? ncu : ntiles, p.splits), dim3(T2), 131072, stream, p);
+    p.persist = (p.splits == 1 && ntiles > ncu) ? 1 : 0;
+    hipLaunchKernelGGL((gemm_nt256_kernel<EPI, OUT_F32, BNT, LN>), dim3(p.persist ? ncu : ntiles, p.splits), dim3(T2), 131072, stream, p);
+    return UENC_OK;
+}
+
+// The two small-shape kernels (register-staged 128 x 128 tiles; K-split 64 x 64 tiles): no dynamic LDS, nothing to set up.
+template <int EPI, int OUT_F32>
+static int launch_nt_tile128(GemmNT& p, int batch, hipStream_t stream) {
+    p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
+    hipLaunchKernelGGL((gemm_nt_kernel<EPI, OUT_F32>), dim3(p.tiles_m * p.tiles_n, p.splits, batch), dim3(GEMM_THREADS), 0, stream, p);
+    return UENC_OK;
+}
+
+template <int EPI, int OUT_F32>
+static int launch_nt_skinny(GemmNT& p, hipStream_t stream) {
+    p.tiles_m = (p.M + 63) / 64; p.tiles_n = (p.N + 63) / 64;
+    const dim3 grid(p.tiles_m * p.tiles_n), block(GEMM_THREADS);
+    if (p.a_f32) hipLaunchKernelGGL((gemm_nt_skinny_kernel<EPI, OUT_F32, 1>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((gemm_nt_skinny_kernel<EPI, OUT_F32, 0>), grid, block, 0, stream, p);
     return UENC_OK;
 }
 
@@ -1272,28 +1205,75 @@ static int launch_nt256(GemmNT& p, hipStream_t stream) {
 // profiles/r03_gemm_nt192_ab.txt): a 192-wide tile costs 0.85-0.92 of a 256-wide one, not 0.75 (its DMA stream runs one k-tile ahead
 // instead of 1.5, and 22 instead of 24 ds_reads feed 48 instead of 64 MFMAs), so it is taken where it saves a round or a quarter-empty
 // column: N = 768 / 2304 at M = 16384 (-8...-10 %), N = 384 (-8...-12 %), N = 4608 / 6144 at M = 4096 (-5...-15 %); neutral on the HBM-bound
-// N = 192 / 576 launches of stage 1.  UENC_GEMM_VARIANT bit 4194304 forces the 192-wide tile wherever it is legal, bit 8388608 forbids it (A/B).
-static bool nt192_wins(int M, int N, int variant) {
-    if (variant & 8388608) return false;
-    if (variant & 4194304) return true;
+// N = 192 / 576 launches of stage 1.
+static bool nt192_wins(int M, int N) {
     const long ncu = nt_cu_count(), tm = (M + BM2 - 1) / BM2;
     const long r256 = (tm * ((N + 255) / 256) + ncu - 1) / ncu, r192 = (tm * ((N + 191) / 192) + ncu - 1) / ncu;
     return r192 * 90 < r256 * 100;
 }
 
 // Which of the two large-tile kernels takes a shape (both compute the same sums in the same k order: identical results).
-// UENC_GEMM_VARIANT bit 131072 forces the two-workgroups-per-CU kernel, bit 262144 the one-workgroup kernel (A/B).
-static bool nt128_wins(int M, int N, int K, int epilogue, int c_dtype, int variant) {
-    if (variant & 262144) return false;
-    if (variant & 131072) return true;
+static bool nt128_wins(int M, int N, int K, int c_dtype) {
     // Measured per workload shape (tools/gemm_nt128_ab.py -> profiles/r03_gemm_nt128_ab.txt): the half-height kernel wins 3-15 % where a
     // single 256-wide column of tiles covers N and the contraction is short (the deformable encoder's K = 256 projections and its
     // 1024 -> 256 FFN GEMM with the fp32 residual epilogue, the decoder's key / value projections over the 1/4-resolution map): every
     // A row is read once and the launch is store-bound.  Everywhere else its 1.5 x L2 -> LDS traffic and 1.5 x DMA instructions per
     // MFMA cost 4-30 %.
-    (void)epilogue;
     if (c_dtype == UENC_BF16 && M > 200000) return false;          // (262144, 256, 256) -> bf16: 6 % slower
     return N > 192 && N <= 288 && K <= 1024;
+}
+
+// The kernel that takes a shape.  Legality first; where two LDS-DMA kernels are legal the measured choosers above decide, or the
+// caller's `tile` (UENC_NT_TILE_*: the tests and the A/B tools pin a kernel with it).  `tile` replaces the choosers' answer only: a
+// shape the named kernel does not take is refused, never sent elsewhere.  summed = split-K / accumulate (fp32 atomics) or stored partials.
+enum NtRoute { NT_REFUSED = -1, NT_TILE128, NT_SKINNY, NT_HALF, NT_256, NT_192 };
+
+static NtRoute nt_route(int M, int N, int K, int batch, int a_dtype, long lda, int c_dtype, int epilogue, bool summed, int klen, int splitk,
+                        bool ln, int tile) {
+    const bool prefer_half = tile == 0 ? nt128_wins(M, N, K, c_dtype) : tile == UENC_NT_TILE_128X256;
+    // what the three LDS-DMA kernels share: bf16 A, no batch; a 192-wide output still wins on the 256 tile (A is streamed once, not twice)
+    const bool dma = batch == 1 && a_dtype == UENC_BF16 && K >= 128 && lda % 8 == 0 && N >= 192 && N % 8 == 0;
+    // (a contraction that is a multiple of 32 but not of 64 -- the 288 columns of the deformable encoder's offset / weight projection -- fits the
+    // half-height kernel's 32-wide k-steps: it goes there when that kernel is the choice anyway, instead of to the register-staged one)
+    const bool k32 = (K % BK != 0) && (K % BK3 == 0) && !summed && prefer_half;
+    // large-tile path: K a multiple of 64, enough 256x256 tiles to fill most CUs (split-K: a single skinny tile measured faster on the 128x128 kernel)
+    const long tiles256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+    const bool big = dma && ((K % BK == 0) || k32) &&
+                     (summed ? (epilogue == EPI_NONE && c_dtype == UENC_F32 && klen % BK == 0 && tiles256 >= 4 && tiles256 * splitk >= 64) : tiles256 >= 160);
+    // too few 256 x 256 tiles for the one-workgroup-per-CU kernel, but >= 96 tiles of 128 x 256 (stage 4 of Swin-L: M = 4096, N = 1536: 192; the
+    // key / value projections of the decoder's smaller pyramid levels): the half-height kernel instead of the register-staged 128 x 128 one
+    // (profiles/r03_gemm_mid_ab.txt)
+    const long htiles = (long)((M + 127) / 128) * ((N + 255) / 256);
+    const bool mid = !big && dma && (K % BK == 0) && !summed && htiles >= 96 &&
+                     (c_dtype == UENC_F32 ? (epilogue == EPI_NONE || epilogue == EPI_RESIDUAL || epilogue == EPI_RELU) : true);
+    if (tile != 0 && !big) return NT_REFUSED;
+    if (ln && !(big || mid)) return NT_REFUSED;       // (the small-shape kernels have no row-wide epilogue: the caller runs LayerNorm itself)
+    // few output tiles (the decoder's M = 300-row GEMMs): the K-split 64 x 64 kernel
+    const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    if (!big && batch == 1 && !summed && tiles128 <= 32 && K >= 64) return NT_SKINNY;
+    if (!(big || mid)) return NT_TILE128;
+    if (mid || (!summed && (K % BK3 == 0) && prefer_half)) return NT_HALF;
+    if (tile == UENC_NT_TILE_128X256) return NT_REFUSED;
+    const bool narrow_ok = !summed && !(ln && N > 192);       // (fused LayerNorm: the row must sit in ONE column tile)
+    if (tile == UENC_NT_TILE_256X192 && !narrow_ok) return NT_REFUSED;
+    return narrow_ok && (tile == 0 ? nt192_wins(M, N) : tile == UENC_NT_TILE_256X192) ? NT_192 : NT_256;
+}
+
+// One (epilogue, output dtype) instantiation on the routed kernel.  fp32 residual added to a bf16 result (a sum that only feeds the next
+// GEMM) exists on the LDS-DMA kernels only.
+template <int EPI, int OUT_F32>
+static int launch_nt(NtRoute route, GemmNT& p, int batch, hipStream_t stream) {
+    switch (route) {
+        case NT_HALF: return launch_nt128<EPI, OUT_F32>(p, stream);
+        case NT_256: return launch_nt256<EPI, OUT_F32>(p, stream);
+        case NT_192: return launch_nt256<EPI, OUT_F32, 192>(p, stream);
+        default: break;
+    }
+    if constexpr (EPI != EPI_RESIDUAL || OUT_F32) {
+        if (route == NT_SKINNY) return launch_nt_skinny<EPI, OUT_F32>(p, stream);
+        if (route == NT_TILE128) return launch_nt_tile128<EPI, OUT_F32>(p, batch, stream);
+    }
+    return UENC_EINVAL;
 }
 
 struct NtLn { const float* gamma; const float* beta; float* y32; void* y16; float* stats; float eps; };
@@ -1302,7 +1282,7 @@ static int gemm_nt_impl(const void* A, int a_dtype, long lda, const void* W, lon
                         int M, int N, int K, const float* bias, int epilogue, const void* aux, long ldaux,
                         void* aux_out, long ldaux_out, float alpha, int splitk, int accumulate, int batch, long bsA, long bsW,
                         long bsC, hipStream_t stream, long part_stride = 0, const float* sample_scale = nullptr, int rows_per_sample = 0,
-                        const NtLn* ln = nullptr) {
+                        const NtLn* ln = nullptr, int tile = 0) {
     UENC_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0);
     UENC_CHECK_ARG(a_dtype == UENC_F32 || a_dtype == UENC_BF16);
     UENC_CHECK_ARG(c_dtype == UENC_F32 || c_dtype == UENC_BF16);
@@ -1310,17 +1290,17 @@ static int gemm_nt_impl(const void* A, int a_dtype, long lda, const void* W, lon
     UENC_CHECK_ARG(a_dtype == UENC_F32 ? (lda % 4 == 0) : (lda % 8 == 0));
     UENC_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0);
     UENC_CHECK_ARG(epilogue >= EPI_NONE && epilogue <= EPI_MUL_DRELU);
+    UENC_CHECK_ARG(tile == 0 || tile == UENC_NT_TILE_256X256 || tile == UENC_NT_TILE_256X192 || tile == UENC_NT_TILE_128X256);
     if (epilogue >= EPI_RESIDUAL) UENC_CHECK_ARG(aux != nullptr && ldaux % 4 == 0);
     if (splitk < 1) splitk = 1;
     if (splitk > 1 || accumulate) UENC_CHECK_ARG(c_dtype == UENC_F32 && epilogue == EPI_NONE);
     GemmNT p;
-    { const char* e = getenv("UENC_GEMM_VARIANT"); p.variant = e ? atoi(e) : 0; }
     p.A = A; p.a_f32 = (a_dtype == UENC_F32); p.lda = lda;
     p.W = (const bf16*)W; p.ldw = ldw;
     p.C = C; p.ldc = ldc; p.bias = bias; p.aux = aux; p.ldaux = ldaux;
     p.aux_out = (bf16*)aux_out; p.ldaux_out = ldaux_out;
     p.M = M; p.N = N; p.K = K;
-    p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
+    p.tiles_m = 0; p.tiles_n = 0; p.persist = 0;        // (set by the launcher of the routed kernel)
     const int kt = (K + BK - 1) / BK;
     if (splitk > kt) splitk = kt;
     p.klen = ((kt + splitk - 1) / splitk) * BK;
@@ -1340,27 +1320,23 @@ static int gemm_nt_impl(const void* A, int a_dtype, long lda, const void* W, lon
     }
     p.bsA = bsA; p.bsW = bsW; p.bsC = bsC;
     p.ln_gamma = nullptr; p.ln_beta = nullptr; p.ln_y32 = nullptr; p.ln_y16 = nullptr; p.ln_stats = nullptr; p.ln_eps = 0.f;
-    dim3 grid(p.tiles_m * p.tiles_n, splitk, batch), block(GEMM_THREADS);
+
+    // ---- the whole decision, before anything is recorded or launched ----
+    const bool summed = p.atomic || partials;
+    const NtRoute route = nt_route(M, N, K, batch, a_dtype, lda, c_dtype, epilogue, summed, p.klen, splitk, ln != nullptr, tile);
+    if (route == NT_REFUSED) return UENC_EINVAL;
+    const bool dma_kernel = route == NT_HALF || route == NT_256 || route == NT_192;
+    if (c_dtype == UENC_F32) UENC_CHECK_ARG(epilogue == EPI_NONE || epilogue == EPI_RESIDUAL || epilogue == EPI_RELU);
+    else UENC_CHECK_ARG(epilogue != EPI_RESIDUAL || dma_kernel);
+    if (ln != nullptr) {
+        // fused LayerNorm: the row must sit in ONE column tile of an LDS-staged fp32 epilogue
+        UENC_CHECK_ARG(epilogue == EPI_RESIDUAL && c_dtype == UENC_F32 && !summed && N <= 256 && N % 8 == 0 && ldc == N &&
+                       ln->gamma && ln->beta && (ln->y32 || ln->y16));
+        UENC_CHECK_ARG((((uintptr_t)ln->gamma | (uintptr_t)ln->beta | (uintptr_t)ln->y32 | (uintptr_t)ln->y16) & 15) == 0 && ((uintptr_t)ln->stats & 7) == 0);
+        p.ln_gamma = ln->gamma; p.ln_beta = ln->beta; p.ln_y32 = ln->y32; p.ln_y16 = (bf16*)ln->y16; p.ln_stats = (float2*)ln->stats; p.ln_eps = ln->eps;
+    }
+
     const bool prof = uenc_prof_on();
-    // large-tile path: bf16 A, K a multiple of 64, no split-K, enough 256x256 tiles to fill most CUs
-    const long tiles256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-    const int nmin = (p.variant & 64) ? 256 : 192;      // a 192-wide output still wins on the 256 tile: A is streamed once, not twice
-    // (a contraction that is a multiple of 32 but not of 64 -- the 288 columns of the deformable encoder's offset / weight projection -- fits the
-    // half-height kernel's 32-wide k-steps: it goes there when that kernel is the choice anyway, instead of to the register-staged one)
-    const bool k32 = (K % BK != 0) && (K % BK3 == 0) && !p.atomic && !partials && !(p.variant & 33554432) &&
-                     nt128_wins(M, N, K, epilogue, c_dtype, p.variant);
-    const bool big = batch == 1 && a_dtype == UENC_BF16 && ((K % BK == 0) || k32) && K >= 128 && lda % 8 == 0 && !(p.variant & 2) && N >= nmin && N % 8 == 0 &&
-                     ((p.atomic || partials) ? (epilogue == EPI_NONE && c_dtype == UENC_F32 && p.klen % BK == 0 && tiles256 >= 4 && tiles256 * splitk >= 64 &&
-                                  !(p.variant & 16))     // (a single skinny tile measured faster on the 128x128 kernel)
-                               : tiles256 >= 160);
-    // too few 256 x 256 tiles for the one-workgroup-per-CU kernel, but >= 96 tiles of 128 x 256 (stage 4 of Swin-L: M = 4096, N = 1536: 192; the
-    // key / value projections of the decoder's smaller pyramid levels): the half-height kernel instead of the register-staged 128 x 128 one
-    // (bit 2097152 of UENC_GEMM_VARIANT: the old choice, A/B)
-    const long htiles = (long)((M + 127) / 128) * ((N + 255) / 256);
-    const bool mid = !big && batch == 1 && a_dtype == UENC_BF16 && (K % BK == 0) && K >= 128 && lda % 8 == 0 && !(p.variant & 2) && N >= nmin && N % 8 == 0 &&
-                     !p.atomic && !partials && htiles >= 96 && !(p.variant & 2097152) &&
-                     (c_dtype == UENC_F32 ? (epilogue == EPI_NONE || epilogue == EPI_RESIDUAL || epilogue == EPI_RELU) : true);
-    const bool half_tile = mid || (big && !p.atomic && !partials && (K % BK3 == 0) && nt128_wins(M, N, K, epilogue, c_dtype, p.variant));
     if (prof) {
         // algorithmic HBM bytes: A, W and the output once, plus what the epilogue reads (residual / saved activation) or writes besides
         const double mn = (double)M * N;
@@ -1368,94 +1344,25 @@ static int gemm_nt_impl(const void* A, int a_dtype, long lda, const void* W, lon
         if (epilogue == EPI_RESIDUAL) bytes += mn * 4;
         if (epilogue == EPI_MUL_DGELU || epilogue == EPI_MUL_DRELU) bytes += mn * 2;
         if (aux_out != nullptr) bytes += mn * 2;
-        uenc_prof_begin(half_tile ? UENC_PROF_GEMM_NT128 : big ? UENC_PROF_GEMM_NT256 : UENC_PROF_GEMM_NT, 2.0 * batch * M * (double)N * K, stream, batch * bytes);
+        uenc_prof_begin(route == NT_HALF ? UENC_PROF_GEMM_NT128 : dma_kernel ? UENC_PROF_GEMM_NT256 : UENC_PROF_GEMM_NT, 2.0 * batch * M * (double)N * K, stream,
+                        batch * bytes);
     }
-    if (ln != nullptr && !(big || mid)) return UENC_EINVAL;       // (the small-shape kernels have no row-wide epilogue: the caller runs LayerNorm itself)
-    // few output tiles (the decoder's M = 300-row GEMMs): the K-split 64 x 64 kernel
-    const long tiles128 = (long)p.tiles_m * p.tiles_n;
-    if (!big && batch == 1 && !p.atomic && !partials && tiles128 <= 32 && K >= 64 && !(p.variant & 1024)) {
-        GemmNT q = p;
-        q.tiles_m = (M + 63) / 64; q.tiles_n = (N + 63) / 64;
-        const dim3 sgrid(q.tiles_m * q.tiles_n);
-#define LAUNCHS(E, F)                                                                                                      \
-        do {                                                                                                               \
-            if (q.a_f32) hipLaunchKernelGGL((gemm_nt_skinny_kernel<E, F, 1>), sgrid, block, 0, stream, q);               \
-            else hipLaunchKernelGGL((gemm_nt_skinny_kernel<E, F, 0>), sgrid, block, 0, stream, q);                       \
-        } while (0)
-        bool launched = true;
-        if (c_dtype == UENC_F32) {
-            if (epilogue == EPI_NONE) LAUNCHS(EPI_NONE, 1);
-            else if (epilogue == EPI_RESIDUAL) LAUNCHS(EPI_RESIDUAL, 1);
-            else if (epilogue == EPI_RELU) LAUNCHS(EPI_RELU, 1);
-            else launched = false;
-        } else {
-            switch (epilogue) {
-                case EPI_NONE: LAUNCHS(EPI_NONE, 0); break;
-                case EPI_GELU: LAUNCHS(EPI_GELU, 0); break;
-                case EPI_RELU: LAUNCHS(EPI_RELU, 0); break;
-                case EPI_MUL_DGELU: LAUNCHS(EPI_MUL_DGELU, 0); break;
-                case EPI_MUL_DRELU: LAUNCHS(EPI_MUL_DRELU, 0); break;
-                default: launched = false; break;
-            }
-        }
-#undef LAUNCHS
-        if (!launched) return UENC_EINVAL;
-        if (prof) uenc_prof_end(stream);
-        UENC_LAUNCH_RET();
-    }
-    if (big || mid) {
-        int rc = UENC_EINVAL;
-        bool narrow = big && !half_tile && !p.atomic && !partials && nt192_wins(M, N, p.variant);
-        if (ln != nullptr) {
-            // fused LayerNorm: the row must sit in ONE column tile of an LDS-staged fp32 epilogue
-            UENC_CHECK_ARG(epilogue == EPI_RESIDUAL && c_dtype == UENC_F32 && !p.atomic && !partials && N <= 256 && N % 8 == 0 && ldc == N &&
-                           ln->gamma && ln->beta && (ln->y32 || ln->y16) && !(p.variant & 8192));
-            UENC_CHECK_ARG((((uintptr_t)ln->gamma | (uintptr_t)ln->beta | (uintptr_t)ln->y32 | (uintptr_t)ln->y16) & 15) == 0 && ((uintptr_t)ln->stats & 7) == 0);
-            narrow = narrow && N <= 192;
-            p.ln_gamma = ln->gamma; p.ln_beta = ln->beta; p.ln_y32 = ln->y32; p.ln_y16 = (bf16*)ln->y16; p.ln_stats = (float2*)ln->stats; p.ln_eps = ln->eps;
-        }
-#define LAUNCH2(E, F) rc = half_tile ? launch_nt128<E, F>(p, stream) : (p.variant & 128) ? launch_nt256<E, F, 0>(p, stream) : narrow ? launch_nt256<E, F, 1, 192>(p, stream) : launch_nt256<E, F, 1>(p, stream)   /* bit 128: the two-stage loop, for A/B */
-        if (ln != nullptr) {          // (checked above: fp32 residual epilogue, one column tile)
-            rc = half_tile ? launch_nt128<EPI_RESIDUAL, 1, true>(p, stream)
-                           : narrow ? launch_nt256<EPI_RESIDUAL, 1, 1, 192, true>(p, stream) : launch_nt256<EPI_RESIDUAL, 1, 1, BN2, true>(p, stream);
-        } else if (c_dtype == UENC_F32) {
-            if (epilogue == EPI_NONE) LAUNCH2(EPI_NONE, 1);
-            else if (epilogue == EPI_RESIDUAL) LAUNCH2(EPI_RESIDUAL, 1);
-            else if (epilogue == EPI_RELU) LAUNCH2(EPI_RELU, 1);
-        } else {
-            switch (epilogue) {
-                case EPI_NONE: LAUNCH2(EPI_NONE, 0); break;
-                case EPI_GELU: LAUNCH2(EPI_GELU, 0); break;
-                case EPI_RELU: LAUNCH2(EPI_RELU, 0); break;
-                case EPI_MUL_DGELU: LAUNCH2(EPI_MUL_DGELU, 0); break;
-                case EPI_MUL_DRELU: LAUNCH2(EPI_MUL_DRELU, 0); break;
-                case EPI_RESIDUAL: LAUNCH2(EPI_RESIDUAL, 0); break;       // fp32 residual added, bf16 result (a sum that only feeds the next GEMM)
-                default: break;
-            }
-        }
-#undef LAUNCH2
-        if (rc != UENC_OK) return rc;
-        if (prof) uenc_prof_end(stream);
-        UENC_LAUNCH_RET();
-    }
-#define LAUNCH(E, F) hipLaunchKernelGGL((gemm_nt_kernel<E, F>), grid, block, 0, stream, p)
-    if (c_dtype == UENC_F32) {
-        if (epilogue == EPI_NONE) LAUNCH(EPI_NONE, 1);
-        else if (epilogue == EPI_RESIDUAL) LAUNCH(EPI_RESIDUAL, 1);
-        else if (epilogue == EPI_RELU) LAUNCH(EPI_RELU, 1);
-        else return UENC_EINVAL;
+    int rc = UENC_EINVAL;
+    if (ln != nullptr) {          // (checked above: fp32 residual epilogue, one column tile)
+        rc = route == NT_HALF ? launch_nt128<EPI_RESIDUAL, 1, true>(p, stream)
+                              : route == NT_192 ? launch_nt256<EPI_RESIDUAL, 1, 192, true>(p, stream) : launch_nt256<EPI_RESIDUAL, 1, BN2, true>(p, stream);
     } else {
-        switch (epilogue) {
-            case EPI_NONE: LAUNCH(EPI_NONE, 0); break;
-            case EPI_GELU: LAUNCH(EPI_GELU, 0); break;
-            case EPI_RELU: LAUNCH(EPI_RELU, 0); break;
-            case EPI_MUL_DGELU: LAUNCH(EPI_MUL_DGELU, 0); break;
-            case EPI_MUL_DRELU: LAUNCH(EPI_MUL_DRELU, 0); break;
-            default: return UENC_EINVAL;
+        switch (epilogue * 2 + (c_dtype == UENC_F32 ? 1 : 0)) {
+#define NT_CASE(E, F) case (E) * 2 + (F): rc = launch_nt<E, F>(route, p, batch, stream); break
+            NT_CASE(EPI_NONE, 1); NT_CASE(EPI_RESIDUAL, 1); NT_CASE(EPI_RELU, 1);
+            NT_CASE(EPI_NONE, 0); NT_CASE(EPI_GELU, 0); NT_CASE(EPI_RELU, 0); NT_CASE(EPI_MUL_DGELU, 0); NT_CASE(EPI_MUL_DRELU, 0);
+            NT_CASE(EPI_RESIDUAL, 0);
+#undef NT_CASE
+            default: break;
         }
     }
-#undef LAUNCH
-    if (prof) uenc_prof_end(stream);
+    if (prof) uenc_prof_end(stream);       // (also after a launcher's error: a record that was opened is closed)
+    if (rc != UENC_OK) return rc;
     UENC_LAUNCH_RET();
 }
 
@@ -1464,6 +1371,15 @@ extern "C" int uenc_gemm_nt(const void* A, int a_dtype, long lda, const void* W,
                             void* aux_out, long ldaux_out, float alpha, int splitk, int accumulate, hipStream_t stream) {
     return gemm_nt_impl(A, a_dtype, lda, W, ldw, C, c_dtype, ldc, M, N, K, bias, epilogue, aux, ldaux, aux_out, ldaux_out, alpha, splitk,
                         accumulate, 1, 0, 0, 0, stream);
+}
+
+// uenc_gemm_nt on the LDS-DMA kernel the caller names (UENC_NT_TILE_*; 0: as uenc_gemm_nt).  For tests and A/B measurements of the two
+// choosers: returns -1, nothing launched, when the shape is not one that kernel takes.
+extern "C" int uenc_gemm_nt_tile(const void* A, int a_dtype, long lda, const void* W, long ldw, void* C, int c_dtype, long ldc,
+                                 int M, int N, int K, const float* bias, int epilogue, const void* aux, long ldaux,
+                                 void* aux_out, long ldaux_out, float alpha, int splitk, int accumulate, int tile, hipStream_t stream) {
+    return gemm_nt_impl(A, a_dtype, lda, W, ldw, C, c_dtype, ldc, M, N, K, bias, epilogue, aux, ldaux, aux_out, ldaux_out, alpha, splitk,
+                        accumulate, 1, 0, 0, 0, stream, 0, nullptr, 0, nullptr, tile);
 }
 
 // uenc_gemm_nt with alpha multiplied per SAMPLE: C[m][n] = epi(alpha * sample_scale[m / rows_per_sample] * (A W^T + bias)[m][n]).
@@ -1541,7 +1457,6 @@ struct GemmTN {
     int tiles_n, tiles_k;
     int mlen;  // tokens per split (multiple of BK)
     int store; // tnbig only: 1 = the tile is stored (dW = ..., db = ...: single split, no prior zeroing), 0 = added atomically
-    int variant;   // debug A/B switch (UENC_GEMM_VARIANT)
     float alpha;   // multiplies the sums (dW, db) before they are stored / added
 };
 
@@ -1726,8 +1641,8 @@ extern "C" int uenc_gemm_tn_grouped_small(const void* table, int n, int total_it
 // ---------------------------------------------------------------------------------------------
 // Large-tile wgrad: dW[n][k] += sum_m dY[m][n] X[m][k] with a 256(k) x 256(n) output tile, 8 waves.
 // Both operands are token-major, i.e. the contraction index m is the ROW of both images, so neither
-// can be read as a row fragment.  They are brought in untransposed by LDS-DMA (64 tokens x 256
-// columns x 2 operands = 64 KB per stage, two stages) and every MFMA fragment is fetched with the
+// can be read as a row fragment.  They are brought in untransposed by LDS-DMA (32 tokens x 256
+// columns x 2 operands = 32 KB per stage, a ring of four) and every MFMA fragment is fetched with the
 // hardware transposing read ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group): no register
 // transposes, no staging VGPRs.  512-byte rows; 32-byte pieces are XOR-permuted by
 // (row & 3) | ((row >> 3) & 1) << 2 on the DMA source side so that the 8 row-pieces a 32-lane half
@@ -1740,274 +1655,19 @@ __device__ __forceinline__ int tn_off(int row, int col) {        // byte offset 
     return row * (COLS * 2) + piece * 32 + (col & 15) * 2;
 }
 
-// fragment with the contraction index on rows: lane (i = lane & 15 -> column c0 + i; k-slots j' = rows r0 + 8*(lane>>4) + j')
-template <int COLS>
-__device__ __forceinline__ bf16x8 tn_frag(const unsigned char* img, int r0, int c0, int lane) {
-    const int fg = lane >> 4, i = lane & 15, q4 = i >> 2, p4 = i & 3;
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int ra = r0 + 8 * fg + q4, col = c0 + 4 * p4;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + tn_off<COLS>(ra, col)));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + tn_off<COLS>(ra + 4, col)));
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { r[j] = lo[j]; r[4 + j] = hi[j]; }
-    return r;
-}
-
 // TILE = 256: 8 waves (2 x 4), wave tile 128(k) x 64(n), 128 KB LDS, one workgroup per CU.
 // TILE = 128: 4 waves (2 x 2), wave tile  64(k) x 64(n),  64 KB LDS, two workgroups per CU (small N x K outputs, long token ranges).
-template <int TILE>
-__device__ __forceinline__ void tnbig_body(const GemmTN& p, int tile, int msplit) {
-    constexpr int NTHR = TILE * 2, NWN = TILE / 64, WKT = (TILE == 256 ? 8 : 4);     // waves along n; 16-wide k tiles per wave
-    constexpr int IMG = 64 * TILE * 2;                                                   // bytes of one operand image
-    constexpr int RPI = NTHR * 16 / (TILE * 2);                                          // rows filled per DMA instruction
-    constexpr int CPR = TILE / 8;                                                        // 16-byte slots per row
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];                 // 2 stages x (dY + X)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wk = wave / NWN, wn = wave % NWN;
-    const int ntile = tile / p.tiles_k, ktile = tile - ntile * p.tiles_k;
-    const int n0 = ntile * TILE, k0 = ktile * TILE;
-    const int mbeg = msplit * p.mlen;
-    const int mend = min(p.M, mbeg + p.mlen);
-    const int nst = (mend - mbeg) / 64;
-
-    f32x4 acc[WKT][4];
-#pragma unroll
-    for (int i = 0; i < WKT; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // DMA: instruction q fills LDS 16-byte slot L = q * NTHR + t of an image: row L / CPR, position P = L % CPR
-    const bf16* ysrc[4];
-    const bf16* xsrc[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = q * RPI + t / CPR, P = t % CPR;
-        const int piece = (P >> 1) ^ ((row & 3) | (((row >> 3) & 1) << 2));
-        const int col = piece * 16 + (P & 1) * 8;
-        ysrc[q] = (const bf16*)p.dY + (long)(mbeg + row) * p.ldy + min(n0 + col, p.N - 8);
-        xsrc[q] = (const bf16*)p.X + (long)(mbeg + row) * p.ldx + min(k0 + col, p.K - 8);
-    }
-    typedef __attribute__((address_space(3))) void lds_void;
-    auto issue = [&](int st, int stage) {
-        unsigned char* Ys = smem + stage * (2 * IMG);
-        unsigned char* Xs = Ys + IMG;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            __builtin_amdgcn_global_load_lds(ysrc[q] + (long)st * 64 * p.ldy, (lds_void*)(Ys + (q * NTHR + wave * 64) * 16), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(xsrc[q] + (long)st * 64 * p.ldx, (lds_void*)(Xs + (q * NTHR + wave * 64) * 16), 16, 0, 0);
-        }
-    };
-
-    // bias gradient (k-tile 0 only): thread owns 8 columns (one 16-byte chunk) and 4 of the 64 rows of each stage
-    const bool do_db = (p.db != nullptr) && (ktile == 0);
-    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-    if (nst > 0) issue(0, 0);
-    for (int st = 0; st < nst; ++st) {
-        __syncthreads();
-        if (st + 1 < nst) issue(st + 1, (st + 1) & 1);
-        const unsigned char* Ys = smem + (st & 1) * (2 * IMG);
-        const unsigned char* Xs = Ys + IMG;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 kf[WKT], nf[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) nf[j] = tn_frag<TILE>(Ys, ks * 32, wn * 64 + j * 16, lane);
-#pragma unroll
-            for (int i = 0; i < WKT; ++i) kf[i] = tn_frag<TILE>(Xs, ks * 32, wk * (WKT * 16) + i * 16, lane);
-#pragma unroll
-            for (int i = 0; i < WKT; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(kf[i], nf[j], acc[i][j]);
-        }
-        if (do_db) {
-            const int c8 = (t % CPR) * 8, rg = t / CPR;       // 16 row groups
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const bf16x8 v = *(const bf16x8*)(Ys + tn_off<TILE>(rg + 16 * rr, c8));
-#pragma unroll
-                for (int c = 0; c < 8; ++c) bsum[c] += (float)v[c];
-            }
-        }
-    }
-
-    float* T = (float*)smem;
-    constexpr int LDT = TILE + 4;
-    if (do_db) {            // reduce the 16 row-groups through LDS, then one atomic per column
-        __syncthreads();
-        const int c8 = (t % CPR) * 8, rg = t / CPR;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) T[rg * TILE + c8 + c] = bsum[c];
-        __syncthreads();
-        if (t < TILE) {
-            float v = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) v += T[g * TILE + t];
-            if (n0 + t < p.N) { if (p.store == 1) p.db[n0 + t] = v * p.alpha; else atomicAdd(p.db + n0 + t, v * p.alpha); }
-        }
-    }
-    // acc[i][j][r] = dW[n = n0 + wn*64 + j*16 + fr][k = k0 + wk*WKT*16 + i*16 + 4*fg + r]; passes of 64 n-rows
-    const int fr = lane & 15, fg = lane >> 4;
-#pragma unroll
-    for (int ps = 0; ps < NWN; ++ps) {
-        __syncthreads();
-        if (wn == ps) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int i = 0; i < WKT; ++i) *(f32x4*)(T + (j * 16 + fr) * LDT + wk * (WKT * 16) + i * 16 + 4 * fg) = acc[i][j];
-        }
-        __syncthreads();
-        for (int row = wave; row < 64; row += NTHR / 64) {
-            const int n = n0 + ps * 64 + row;
-            if (n >= p.N) break;
-#pragma unroll
-            for (int q = 0; q < TILE / 64; ++q) {
-                const int k = k0 + lane + 64 * q;
-                if (k < p.K) {
-                    if (p.store) p.dW[(long)n * p.ldw + k] = T[row * LDT + lane + 64 * q] * p.alpha;
-                    else atomicAdd(p.dW + (long)n * p.ldw + k, T[row * LDT + lane + 64 * q] * p.alpha);
-                }
-            }
-        }
-    }
-}
-
-// Deep-prefetch form of the same tile (the default): one 64-token stage ahead of the MFMAs (above) leaves 0.86 us -- the stage's
-// 8.4 MFLOP at the CU's peak -- for a DMA that takes 1-2.5 us under load, so the loop ran at the memory LATENCY (~0.7 PFLOP/s
-// whatever the item order or the cache level the panels came from).  Here the ring holds four 32-token stages (one MFMA k-step
-// each, same 128 / 64 KB), the DMA stream runs three stages = 96 tokens ahead, waits are counted (`vmcnt(8)` leaves two stages
-// in flight) and the barrier is a raw s_barrier that does not drain the DMA queue: a stage is read only after the issuing
+// Main loop: a stage's 8.4 MFLOP are 0.86 us at the CU's peak and a DMA takes 1-2.5 us under load, so with one stage ahead the loop
+// ran at the memory LATENCY (~0.7 PFLOP/s whatever the item order or the cache level the panels came from).  The ring holds four
+// 32-token stages (one MFMA k-step each), the DMA stream runs three stages = 96 tokens ahead, waits are counted (`vmcnt(8)` leaves two
+// stages in flight) and the barrier is a raw s_barrier that does not drain the DMA queue: a stage is read only after the issuing
 // waves' counted wait AND the barrier every wave passes after it; its slot is refilled one barrier after its last read.
-template <int TILE>
-__device__ __forceinline__ void tnbig_body_deep(const GemmTN& p, int tile, int msplit) {
-    constexpr int NTHR = TILE * 2, NWN = TILE / 64, WKT = (TILE == 256 ? 8 : 4);
-    constexpr int SR = 32, NS = 4, D = NS - 1;                                           // rows per stage, ring slots, stages in flight
-    constexpr int IMG = SR * TILE * 2;                                                   // bytes of one operand image
-    constexpr int RPI = NTHR * 16 / (TILE * 2);                                          // rows filled per DMA instruction (16)
-    constexpr int CPR = TILE / 8;                                                        // 16-byte slots per row
-    static_assert(RPI == 16, "two DMA instructions per operand and stage");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];                 // NS stages x (dY + X)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wk = wave / NWN, wn = wave % NWN;
-    const int ntile = tile / p.tiles_k, ktile = tile - ntile * p.tiles_k;
-    const int n0 = ntile * TILE, k0 = ktile * TILE;
-    const int mbeg = msplit * p.mlen;
-    const int mend = min(p.M, mbeg + p.mlen);
-    const int nst = (mend - mbeg) / SR;
-
-    f32x4 acc[WKT][4];
-#pragma unroll
-    for (int i = 0; i < WKT; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const bf16* ysrc[2];
-    const bf16* xsrc[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int row = q * RPI + t / CPR, P = t % CPR;
-        const int piece = (P >> 1) ^ ((row & 3) | (((row >> 3) & 1) << 2));
-        const int col = piece * 16 + (P & 1) * 8;
-        ysrc[q] = (const bf16*)p.dY + (long)(mbeg + row) * p.ldy + min(n0 + col, p.N - 8);
-        xsrc[q] = (const bf16*)p.X + (long)(mbeg + row) * p.ldx + min(k0 + col, p.K - 8);
-    }
-    typedef __attribute__((address_space(3))) void lds_void;
-    auto issue = [&](int st) {
-        unsigned char* Ys = smem + (st & (NS - 1)) * (2 * IMG);
-        unsigned char* Xs = Ys + IMG;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            __builtin_amdgcn_global_load_lds(ysrc[q] + (long)st * SR * p.ldy, (lds_void*)(Ys + (q * NTHR + wave * 64) * 16), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(xsrc[q] + (long)st * SR * p.ldx, (lds_void*)(Xs + (q * NTHR + wave * 64) * 16), 16, 0, 0);
-        }
-    };
-
-    const bool do_db = (p.db != nullptr) && (ktile == 0);
-    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-        if (i < nst) issue(i);
-    for (int st = 0; st < nst; ++st) {
-        // stage st has landed (this wave's pieces) once at most the min(D - 1, stages after st) younger stages are outstanding
-        wait_vmcnt_upto8(4 * min(D - 1, nst - 1 - st));
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();                        // ... and everyone's; every wave is also past its reads of stage st - 1
-        __builtin_amdgcn_sched_barrier(0);
-        if (st + D < nst) issue(st + D);                     // into the slot of stage st - 1
-        const unsigned char* Ys = smem + (st & (NS - 1)) * (2 * IMG);
-        const unsigned char* Xs = Ys + IMG;
-        bf16x8 kf[WKT], nf[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) nf[j] = tn_frag<TILE>(Ys, 0, wn * 64 + j * 16, lane);
-#pragma unroll
-        for (int i = 0; i < WKT; ++i) kf[i] = tn_frag<TILE>(Xs, 0, wk * (WKT * 16) + i * 16, lane);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < WKT; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(kf[i], nf[j], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        if (do_db) {
-            const int c8 = (t % CPR) * 8, rg = t / CPR;       // 16 row groups
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const bf16x8 v = *(const bf16x8*)(Ys + tn_off<TILE>(rg + 16 * rr, c8));
-#pragma unroll
-                for (int c = 0; c < 8; ++c) bsum[c] += (float)v[c];
-            }
-        }
-    }
-
-    float* T = (float*)smem;
-    constexpr int LDT = TILE + 4;
-    if (do_db) {            // reduce the 16 row-groups through LDS, then one atomic per column
-        __syncthreads();
-        const int c8 = (t % CPR) * 8, rg = t / CPR;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) T[rg * TILE + c8 + c] = bsum[c];
-        __syncthreads();
-        if (t < TILE) {
-            float v = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) v += T[g * TILE + t];
-            if (n0 + t < p.N) { if (p.store == 1) p.db[n0 + t] = v * p.alpha; else atomicAdd(p.db + n0 + t, v * p.alpha); }
-        }
-    }
-    const int fr = lane & 15, fg = lane >> 4;
-#pragma unroll
-    for (int ps = 0; ps < NWN; ++ps) {
-        __syncthreads();
-        if (wn == ps) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int i = 0; i < WKT; ++i) *(f32x4*)(T + (j * 16 + fr) * LDT + wk * (WKT * 16) + i * 16 + 4 * fg) = acc[i][j];
-        }
-        __syncthreads();
-        for (int row = wave; row < 64; row += NTHR / 64) {
-            const int n = n0 + ps * 64 + row;
-            if (n >= p.N) break;
-#pragma unroll
-            for (int q = 0; q < TILE / 64; ++q) {
-                const int k = k0 + lane + 64 * q;
-                if (k < p.K) {
-                    if (p.store) p.dW[(long)n * p.ldw + k] = T[row * LDT + lane + 64 * q] * p.alpha;
-                    else atomicAdd(p.dW + (long)n * p.ldw + k, T[row * LDT + lane + 64 * q] * p.alpha);
-                }
-            }
-        }
-    }
-}
-
-// Hand-scheduled form of the deep-prefetch loop.  In tnbig_body_deep hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the
-// first transposing LDS read of every stage (an LDS read with a memory operand waits for ALL LDS-DMA in flight) and
-// `lgkmcnt(0)` in front of the first MFMA: the DMA ring is drained every 32 tokens and no read overlaps an MFMA -- it measured
-// 10-30 % SLOWER than the two-stage loop.  Here the fragment reads are inline asm (invisible to the waitcnt pass), issued at
-// most 14 deep (lgkmcnt is a 4-bit counter), each group of four MFMAs waits with a counted lgkmcnt for exactly the fragment it
-// consumes, and the bias gradient comes from four extra MFMAs against an all-ones fragment instead of LDS row sums.
+// The fragment reads are hand-scheduled: written as builtins, hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the first
+// transposing LDS read of every stage (an LDS read with a memory operand waits for ALL LDS-DMA in flight) and `lgkmcnt(0)` in front
+// of the first MFMA: the DMA ring is drained every 32 tokens and no read overlaps an MFMA -- 10-30 % SLOWER than one stage ahead.
+// Here the reads are inline asm (invisible to the waitcnt pass), issued at most 14 deep (lgkmcnt is a 4-bit counter), each group of
+// four MFMAs waits with a counted lgkmcnt for exactly the fragment it consumes, and the bias gradient comes from four extra MFMAs
+// against an all-ones fragment instead of LDS row sums.
 template <int ROW4>
 __device__ __forceinline__ void ds_tr_pair(bf16x8& f, unsigned addr) {
     bf16x4 lo, hi;
@@ -2147,9 +1807,7 @@ __device__ __forceinline__ void tnbig_body_asm(const GemmTN& p, int tile, int ms
 
 template <int TILE>
 __global__ __launch_bounds__(TILE * 2) void gemm_tnbig_kernel(GemmTN p) {
-    if (p.variant & 2048) tnbig_body<TILE>(p, blockIdx.x, blockIdx.y);      // bit 2048: the round-1 main loop, for A/B
-    else if (p.variant & 4096) tnbig_body_deep<TILE>(p, blockIdx.x, blockIdx.y);   // bit 4096: deep ring, compiler-scheduled reads
-    else tnbig_body_asm<TILE>(p, blockIdx.x, blockIdx.y);
+    tnbig_body_asm<TILE>(p, blockIdx.x, blockIdx.y);
 }
 
 // Grouped form: ONE launch computes many weight gradients.  The backward of a layer leaves 4 small-output wgrad GEMMs
@@ -2166,21 +1824,18 @@ struct TnGroupDesc {
     float alpha; int pad_;    // alpha multiplies the sums; 0 is read as 1
 };
 
-// Item order (XCD_WINDOWS): what shares operand panels must run on ONE XCD at the same time, or every tile re-fetches its
+// Item order: what shares operand panels must run on ONE XCD at the same time, or every tile re-fetches its
 // dY / X panels from the fabric (measured round 1: 44 GB per step against ~19 GB read once).  Logical items are ordered
 // (descriptor, token split, tile) with the tile fastest, so W consecutive items -- W = the workgroups an XCD runs at once -- are
 // the tiles of one weight over the SAME token range: together they read each 64-token panel piece once into the XCD's L2.
 // Hardware block b runs on XCD slot b % 8 as that slot's (b / 8)-th block: window c of the logical list goes to slot c % 8.
 // Placement is for speed only (any mapping gives the same sums).
-template <int TILE, bool XCD_WINDOWS>
-__global__ __launch_bounds__(TILE * 2) void gemm_tnbig_grouped_kernel(const TnGroupDesc* __restrict__ table, int n, int total, int deep) {
-    int item = blockIdx.x;
-    if (XCD_WINDOWS) {
-        constexpr int WIN = TILE == 256 ? 32 : 64;
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-        item = ((j / WIN) * 8 + x) * WIN + (j % WIN);
-        if (item >= total) return;
-    }
+template <int TILE>
+__global__ __launch_bounds__(TILE * 2) void gemm_tnbig_grouped_kernel(const TnGroupDesc* __restrict__ table, int n, int total) {
+    constexpr int WIN = TILE == 256 ? 32 : 64;
+    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
+    const int item = ((j / WIN) * 8 + x) * WIN + (j % WIN);
+    if (item >= total) return;
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -2190,18 +1845,10 @@ __global__ __launch_bounds__(TILE * 2) void gemm_tnbig_grouped_kernel(const TnGr
     GemmTN p;
     p.dY = d.dY; p.dy_f32 = 0; p.ldy = d.ldy; p.X = d.X; p.x_f32 = 0; p.ldx = d.ldx;
     p.dW = d.dW; p.ldw = d.ldw; p.db = d.db; p.M = d.M; p.N = d.N; p.K = d.K;
-    p.tiles_n = 0; p.tiles_k = d.tiles_k; p.mlen = d.mlen; p.store = d.nsplit == 1 ? d.store : 0; p.variant = 0; p.alpha = d.alpha == 0.f ? 1.f : d.alpha;
+    p.tiles_n = 0; p.tiles_k = d.tiles_k; p.mlen = d.mlen; p.store = d.nsplit == 1 ? d.store : 0; p.alpha = d.alpha == 0.f ? 1.f : d.alpha;
     const int local = item - d.item_begin;
-    int tile, msplit;
-    if (XCD_WINDOWS) {
-        const int ntiles = ((d.N + TILE - 1) / TILE) * d.tiles_k;
-        tile = local % ntiles; msplit = local / ntiles;
-    } else {
-        tile = local / d.nsplit; msplit = local % d.nsplit;
-    }
-    if (deep == 2) tnbig_body_asm<TILE>(p, tile, msplit);
-    else if (deep == 1) tnbig_body_deep<TILE>(p, tile, msplit);
-    else tnbig_body<TILE>(p, tile, msplit);
+    const int ntiles = ((d.N + TILE - 1) / TILE) * d.tiles_k;
+    tnbig_body_asm<TILE>(p, local % ntiles, local / ntiles);
 }
 
 // table: n descriptors (device memory) of 96 bytes {dY, X, dW, db, ldy, ldx, ldw, M, N, K, tiles_k, mlen, nsplit, item_begin, store, alpha (float; 0 = 1), 0}:
@@ -2214,29 +1861,19 @@ extern "C" int uenc_gemm_tn_grouped(const void* table, int n, int total_items, i
     static_assert(sizeof(TnGroupDesc) == 96, "descriptor layout is part of the ABI");
     static bool attr_set = false;
     if (!attr_set) {
-        const void* fns[4] = {(const void*)gemm_tnbig_grouped_kernel<256, true>, (const void*)gemm_tnbig_grouped_kernel<256, false>,
-                              (const void*)gemm_tnbig_grouped_kernel<128, true>, (const void*)gemm_tnbig_grouped_kernel<128, false>};
-        for (int i = 0; i < 4; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * (i < 2 ? 256 : 128) * 2);
+        const void* fns[2] = {(const void*)gemm_tnbig_grouped_kernel<256>, (const void*)gemm_tnbig_grouped_kernel<128>};
+        for (int i = 0; i < 2; ++i) {
+            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * (i < 1 ? 256 : 128) * 2);
             if (e != hipSuccess) return (int)e;
         }
         attr_set = true;
     }
     const bool prof = uenc_prof_on();
     if (prof) uenc_prof_begin(UENC_PROF_GEMM_TN, flops, stream);          // flops: 2 * sum(M N K), for the profiler only
-    const char* ev = getenv("UENC_GEMM_VARIANT");
-    const bool windows = !(ev && (atoi(ev) & 512));                       // bit 512: the round-1 item order (tile-major, split fastest), for A/B
-    const int evv = ev ? atoi(ev) : 0;
-    const int deep = (evv & 2048) ? 0 : (evv & 4096) ? 1 : 2;             // bit 2048: the round-1 main loop; bit 4096: deep ring with compiler-scheduled reads
     const int win = 8 * (tile == 256 ? 32 : 64);
-    const unsigned grid = windows ? (unsigned)((total_items + win - 1) / win * win) : (unsigned)total_items;
-    if (tile == 256) {
-        if (windows) hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<256, true>), dim3(grid), dim3(512), 4 * 64 * 256 * 2, stream, (const TnGroupDesc*)table, n, total_items, deep);
-        else hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<256, false>), dim3(grid), dim3(512), 4 * 64 * 256 * 2, stream, (const TnGroupDesc*)table, n, total_items, deep);
-    } else {
-        if (windows) hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<128, true>), dim3(grid), dim3(256), 4 * 64 * 128 * 2, stream, (const TnGroupDesc*)table, n, total_items, deep);
-        else hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<128, false>), dim3(grid), dim3(256), 4 * 64 * 128 * 2, stream, (const TnGroupDesc*)table, n, total_items, deep);
-    }
+    const unsigned grid = (unsigned)((total_items + win - 1) / win * win);
+    if (tile == 256) hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<256>), dim3(grid), dim3(512), 4 * 64 * 256 * 2, stream, (const TnGroupDesc*)table, n, total_items);
+    else hipLaunchKernelGGL((gemm_tnbig_grouped_kernel<128>), dim3(grid), dim3(256), 4 * 64 * 128 * 2, stream, (const TnGroupDesc*)table, n, total_items);
     if (prof) uenc_prof_end(stream);
     UENC_LAUNCH_RET();
 }
@@ -2266,8 +1903,9 @@ static int launch_tnbig(GemmTN& p, int M, int N, int K, int splitm, int max_spli
 }
 
 static int gemm_tn_impl(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,
-                        float* db, int M, int N, int K, int splitm, float alpha, hipStream_t stream) {
+                        float* db, int M, int N, int K, int splitm, float alpha, hipStream_t stream, int tile = 0) {
     UENC_CHECK_ARG(dY && X && dW && M > 0 && N > 0 && K > 0);
+    UENC_CHECK_ARG(tile == 0 || tile == 128 || tile == 256);
     UENC_CHECK_ARG(N % 8 == 0 && K % 8 == 0);
     UENC_CHECK_ARG(dy_dtype == UENC_F32 ? (ldy % 4 == 0) : (dy_dtype == UENC_BF16 && ldy % 8 == 0));
     UENC_CHECK_ARG(x_dtype == UENC_F32 ? (ldx % 4 == 0) : (x_dtype == UENC_BF16 && ldx % 8 == 0));
@@ -2275,18 +1913,17 @@ static int gemm_tn_impl(const void* dY, int dy_dtype, long ldy, const void* X, i
     GemmTN p;
     p.dY = dY; p.dy_f32 = (dy_dtype == UENC_F32); p.ldy = ldy; p.X = X; p.x_f32 = (x_dtype == UENC_F32); p.ldx = ldx;
     p.dW = dW; p.ldw = ldw; p.db = db; p.M = M; p.N = N; p.K = K; p.store = 0; p.alpha = alpha;
-    { const char* e0 = getenv("UENC_GEMM_VARIANT"); p.variant = e0 ? atoi(e0) : 0; }
     // LDS-DMA paths: bf16 operands, whole 64-token stages.  256x256 tiles when the output has >= 20 of them (every split
     // of the token range costs a 256 KB atomic burst per tile, so splits are capped at 8); else 128x128 tiles, whose
-    // outputs are small enough to split the token range much further.
-    { const char* e = getenv("UENC_GEMM_VARIANT"); const int variant = e ? atoi(e) : 0;
-      if (dy_dtype == UENC_BF16 && x_dtype == UENC_BF16 && M % 64 == 0 && M >= 2048 && !(variant & 4)) {
+    // outputs are small enough to split the token range much further.  `tile` (tests) replaces that rule's answer only.
+    const bool dma = dy_dtype == UENC_BF16 && x_dtype == UENC_BF16 && M % 64 == 0 && M >= 2048;
+    if (tile != 0 && !dma) return UENC_EINVAL;
+    if (dma) {
         int rc;
-        if ((variant & 8) || (long)((N + 255) / 256) * ((K + 255) / 256) >= 20) rc = launch_tnbig<256>(p, M, N, K, splitm, 8, stream);
+        if (tile != 0 ? tile == 256 : (long)((N + 255) / 256) * ((K + 255) / 256) >= 20) rc = launch_tnbig<256>(p, M, N, K, splitm, 8, stream);
         else rc = launch_tnbig<128>(p, M, N, K, splitm, 64, stream);
         if (rc != UENC_OK) return rc;
         UENC_LAUNCH_RET();
-      }
     }
     p.tiles_n = (N + BN - 1) / BN; p.tiles_k = (K + BM - 1) / BM;
     const int mt = (M + BK - 1) / BK;
@@ -2312,6 +1949,13 @@ static int gemm_tn_impl(const void* dY, int dy_dtype, long ldy, const void* X, i
 extern "C" int uenc_gemm_tn(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,
                             float* db, int M, int N, int K, int splitm, hipStream_t stream) {
     return gemm_tn_impl(dY, dy_dtype, ldy, X, x_dtype, ldx, dW, ldw, db, M, N, K, splitm, 1.0f, stream);
+}
+
+// uenc_gemm_tn on the LDS-DMA kernel with the output tile the caller names (256 or 128; 0: as uenc_gemm_tn).  For tests: returns -1,
+// nothing launched, unless both operands are bf16, M % 64 == 0 and M >= 2048.
+extern "C" int uenc_gemm_tn_tile(const void* dY, int dy_dtype, long ldy, const void* X, int x_dtype, long ldx, float* dW, long ldw,
+                                 float* db, int M, int N, int K, int splitm, int tile, hipStream_t stream) {
+    return gemm_tn_impl(dY, dy_dtype, ldy, X, x_dtype, ldx, dW, ldw, db, M, N, K, splitm, 1.0f, stream, tile);
 }
 
 // dW += alpha * dY^T X, db += alpha * column sums of dY (the weight gradient of a branch whose output was scaled by alpha: DropPath)

@@ -15,6 +15,7 @@ from .capi import BF16, F32, check, dt, lib, ptr, stream_ptr
 
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU = (
     capi.EPI_NONE, capi.EPI_GELU, capi.EPI_RELU, capi.EPI_RESIDUAL, capi.EPI_MUL_DGELU, capi.EPI_MUL_DRELU)
+NT_TILE_256X256, NT_TILE_256X192, NT_TILE_128X256 = 256, 192, 128       # UENC_NT_TILE_* of include/uenc.h (gemm_nt's `tile`)
 
 
 # fp32 "exact" arithmetic mode (csrc/exact.hip): every activation that is bf16 between kernels in the
@@ -210,9 +211,12 @@ def cast_transpose_bf16(src: torch.Tensor, out: Optional[torch.Tensor] = None) -
 def gemm_nt(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
             aux: Optional[torch.Tensor] = None, aux_out: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16, alpha: float = 1.0,
-            splitk: int = 1, accumulate: bool = False, sample_scale: Optional[torch.Tensor] = None, rows_per_sample: int = 0) -> torch.Tensor:
+            splitk: int = 1, accumulate: bool = False, sample_scale: Optional[torch.Tensor] = None, rows_per_sample: int = 0,
+            tile: int = 0) -> torch.Tensor:
     """out[m, n] = epi(alpha * (sum_k a[m, k] * w[n, k] + bias[n])).  a fp32|bf16, w bf16, fp32 accumulate.
-    sample_scale (device fp32, one entry per `rows_per_sample` rows): alpha is multiplied by the row's sample scale (DropPath)."""
+    sample_scale (device fp32, one entry per `rows_per_sample` rows): alpha is multiplied by the row's sample scale (DropPath).
+    tile (tests, A/B tools): NT_TILE_256X256 / NT_TILE_256X192 / NT_TILE_128X256 names the large-tile kernel instead of the library's
+    measured choice; a shape that kernel does not take raises UencError and launches nothing."""
     _mat(a, "a"); _mat(w, "w")
     M, K = a.shape
     N, K2 = w.shape
@@ -237,11 +241,17 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = 
         _mat(aux_out, "aux_out"); assert aux_out.shape == (M, N) and aux_out.dtype == torch.bfloat16
     if sample_scale is not None:
         assert sample_scale.dtype == torch.float32 and sample_scale.is_cuda and sample_scale.is_contiguous()
-        assert rows_per_sample > 0 and sample_scale.numel() * rows_per_sample >= M and splitk == 1 and not accumulate
+        assert rows_per_sample > 0 and sample_scale.numel() * rows_per_sample >= M and splitk == 1 and not accumulate and tile == 0
         check(lib.uenc_gemm_nt_scaled(a.data_ptr(), dt(a), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), dt(out),
                                       out.stride(0), M, N, K, ptr(bias), epilogue, ptr(aux), aux.stride(0) if aux is not None else 0,
                                       ptr(aux_out), aux_out.stride(0) if aux_out is not None else 0, float(alpha), sample_scale.data_ptr(),
                                       int(rows_per_sample), stream_ptr()), "gemm_nt_scaled")
+        return out
+    if tile != 0:
+        check(lib.uenc_gemm_nt_tile(a.data_ptr(), dt(a), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), dt(out),
+                                    out.stride(0), M, N, K, ptr(bias), epilogue, ptr(aux), aux.stride(0) if aux is not None else 0,
+                                    ptr(aux_out), aux_out.stride(0) if aux_out is not None else 0, float(alpha), int(splitk),
+                                    int(accumulate), int(tile), stream_ptr()), "gemm_nt_tile")
         return out
     check(lib.uenc_gemm_nt(a.data_ptr(), dt(a), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), dt(out),
                            out.stride(0), M, N, K, ptr(bias), epilogue, ptr(aux), aux.stride(0) if aux is not None else 0,
@@ -306,8 +316,11 @@ def gemm_nt_batched(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, alph
     return out
 
 
-def gemm_tn(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor] = None, splitm: int = 0, alpha: float = 1.0):
-    """dw[n, k] += alpha * sum_m dy[m, n] * x[m, k];  db[n] += alpha * sum_m dy[m, n].  dy bf16, x fp32|bf16, dw/db fp32 (accumulated)."""
+def gemm_tn(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor] = None, splitm: int = 0, alpha: float = 1.0,
+            tile: int = 0):
+    """dw[n, k] += alpha * sum_m dy[m, n] * x[m, k];  db[n] += alpha * sum_m dy[m, n].  dy bf16, x fp32|bf16, dw/db fp32 (accumulated).
+    tile (tests): 256 or 128 names the output tile of the LDS-DMA kernel instead of the library's choice; operands it does not take
+    (not both bf16, M % 64 != 0, M < 2048) raise UencError and launch nothing."""
     _mat(dy, "dy"); _mat(x, "x"); _mat(dw, "dw")
     M, N = dy.shape
     M2, K = x.shape
@@ -321,8 +334,13 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[to
                                    stream_ptr()), "gemm_tn_f32")
         return
     if alpha != 1.0:
+        assert tile == 0
         check(lib.uenc_gemm_tn_scaled(dy.data_ptr(), dt(dy), dy.stride(0), x.data_ptr(), dt(x), x.stride(0), dw.data_ptr(), dw.stride(0),
                                       ptr(db), M, N, K, int(splitm), float(alpha), stream_ptr()), "gemm_tn_scaled")
+        return
+    if tile != 0:
+        check(lib.uenc_gemm_tn_tile(dy.data_ptr(), dt(dy), dy.stride(0), x.data_ptr(), dt(x), x.stride(0), dw.data_ptr(), dw.stride(0),
+                                    ptr(db), M, N, K, int(splitm), int(tile), stream_ptr()), "gemm_tn_tile")
         return
     check(lib.uenc_gemm_tn(dy.data_ptr(), dt(dy), dy.stride(0), x.data_ptr(), dt(x), x.stride(0), dw.data_ptr(), dw.stride(0),
                            ptr(db), M, N, K, int(splitm), stream_ptr()), "gemm_tn")
