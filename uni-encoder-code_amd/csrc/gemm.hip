@@ -256,11 +256,17 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_nt_kernel(GemmNT p) {
 
 
 // ---------------------------------------------------------------------------------------------
-// Skinny kernel for the GEMMs with a handful of output tiles (the transformer decoder: M = B * 150 query rows, N = 256 ... 2048,
-// K up to 2048; ~250 launches per step that ran 6 ... 48 workgroups of the 128-tile kernel for 10 ... 25 us each, every k-tile
-// paying a full memory latency).  Here a workgroup owns a 64 x 64 tile and its four waves split the K range between them:
-// fragments go global -> registers directly in MFMA layout (nothing is shared between waves, so no LDS staging), 4 k-steps
-// (32 loads per lane) in flight per iteration, the four partial tiles are summed through LDS and the epilogue runs once.
+// Few-row kernel for the GEMMs whose output is small (the transformer decoder: M = B * 150 query rows, N = 256 ... 2048, K up to
+// 2048, and the key / value projections of its smallest map; ~270 launches per step).  The time of such a launch is one workgroup's
+// latency until the workgroups outnumber the CUs, so the tile is SMALL: the launcher picks the wave tile (16 x 32 or 32 x 32) that
+// puts between half and all of the CUs to work.  Fragments go global -> registers directly in MFMA layout (no LDS staging), four
+// 32-wide k-steps per register buffer, two buffers: the next buffer's loads are in flight while this one's MFMAs run, and no load is
+// issued for a k-position outside the wave's k-range.
+//   NR == 4: the workgroup owns ONE wave tile and wave w sums k-range w = [w * per * 32, min(K, (w + 1) * per * 32)),
+//            per = ceil(ceil(K / 32) / 4); the four partial tiles are added through LDS as (((0 + p0) + p1) + p2) + p3.
+//   NR == 1: 2 x 2 waves with a wave tile each, every wave one chain over all k-steps (the sums of gemm_nt_kernel).
+// Either way each chain runs its k-steps in ascending order from a zero accumulator, positions past the range's end are zero, then
+// + bias, * alpha and the epilogue: which tile a shape gets never changes a result bit.
 // ---------------------------------------------------------------------------------------------
 template <int EPI, int OUT_F32>
 __device__ __forceinline__ void epilogue8(const GemmNT& p, int m, int n, bool full8, float (&v)[8]) {
@@ -310,87 +316,141 @@ __device__ __forceinline__ void epilogue8(const GemmNT& p, int m, int n, bool fu
     }
 }
 
-template <int EPI, int OUT_F32, int A_F32>
-__global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(GemmNT p) {
-    constexpr int LDP = 68;                                   // 64 + 4: the accumulator writes are bank-conflict free
-    __shared__ __attribute__((aligned(16))) float part[4 * 64 * LDP];
+#define FR_CH 4          // 32-wide k-steps per register buffer
+
+// a * b rounded on its own, never contracted into the residual add that follows it: the K-split kernel this one replaced rounded the
+// alpha product before the epilogue, and the results stay its results bit for bit
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// One register buffer of the few-row kernel: the raw fragments of FR_CH k-steps (fp32 A stays fp32 until its MFMA: a conversion at
+// load time would wait for the load)
+template <int A_F32, int MT, int NTL>
+struct FewRowBuf {
+    u32x4 a[FR_CH][MT][A_F32 ? 2 : 1];
+    u32x4 w[FR_CH][NTL];
+};
+
+template <int EPI, int OUT_F32, int A_F32, int NR, int MT, int NTL>
+__global__ __launch_bounds__(256) void gemm_nt_fewrow_kernel(GemmNT p) {
+    static_assert(NR == 4 || NR == 1, "four k-ranges summed in order, or one chain");
+    constexpr int WM = MT * 16, WN = NTL * 16;                // wave tile
+    constexpr int TM = NR == 4 ? WM : 2 * WM, TN = NR == 4 ? WN : 2 * WN;      // workgroup tile
+    constexpr int LDP = TN + 4;                               // the accumulator writes are bank-conflict free
+    __shared__ __attribute__((aligned(16))) float part[NR * TM * LDP];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int mt = blockIdx.x / p.tiles_n, nt = blockIdx.x - mt * p.tiles_n;
-    const int m0 = mt * 64, n0 = nt * 64;
-    const int per = (((p.K + 31) >> 5) + 3) >> 2;             // 32-wide k-steps per wave
-    const int kb = wave * per * 32, ke = min(p.K, kb + per * 32);
+    const int m0 = mt * TM, n0 = nt * TN;
+    const int wm = NR == 4 ? 0 : (wave >> 1), wn = NR == 4 ? 0 : (wave & 1);
+    const int mw = m0 + wm * WM, nw = n0 + wn * WN;           // this wave's tile
+    const int per = (((p.K + 31) >> 5) + 3) >> 2;             // 32-wide k-steps per k-range
+    const int kb = NR == 4 ? wave * per * 32 : 0;
+    // (a wave tile that lies outside the matrix has an empty k-range: it loads nothing and stores zeros nobody reads)
+    const int ke = (mw < p.M && nw < p.N) ? (NR == 4 ? min(p.K, kb + per * 32) : p.K) : kb;
 
-    f32x4 acc[4][4];
+    f32x4 acc[NTL][MT];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < NTL; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    long aoff[4], woff[4];
+        for (int j = 0; j < MT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const char* ap[MT];
+    const bf16* wp[NTL];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        aoff[j] = (long)min(m0 + j * 16 + fr, p.M - 1) * p.lda;
-        woff[j] = (long)min(n0 + j * 16 + fr, p.N - 1) * p.ldw;
-    }
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    for (int k = kb; k < ke; k += 128) {
-        u32x4 xa[4][4], wa[4][4];
+    for (int j = 0; j < MT; ++j) ap[j] = (const char*)p.A + ((long)min(mw + j * 16 + fr, p.M - 1) * p.lda + 8 * fg) * (A_F32 ? 4 : 2);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int kk = k + s * 32 + 8 * fg;
-            const bool ok = kk < ke;
-            const int kc = min(kk, p.K - 8);                  // clamped address, masked value: the loads stay unconditional
+    for (int i = 0; i < NTL; ++i) wp[i] = p.W + (long)min(nw + i * 16 + fr, p.N - 1) * p.ldw + 8 * fg;
+
+    using Buf = FewRowBuf<A_F32, MT, NTL>;
+    // the fragments of k-steps k, k + 32, ...: lane group fg holds k-offsets 8 fg .. 8 fg + 7 of a step, zero at or past the range's end
+    auto load = [&](Buf& b, int k) {
+        const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (A_F32) {
-                    const float* ap = (const float*)p.A + aoff[j] + kc;
-                    const float4 a0 = *(const float4*)ap, a1 = *(const float4*)(ap + 4);
-                    const bf16x8 r = cvt8(a0, a1);
-                    xa[s][j] = ok ? *(const u32x4*)&r : z;
-                } else {
-                    const u32x4 v = *(const u32x4*)((const bf16*)p.A + aoff[j] + kc);
-                    xa[s][j] = ok ? v : z;
-                }
-                const u32x4 w = *(const u32x4*)(p.W + woff[j] + kc);
-                wa[s][j] = ok ? w : z;
+        for (int s = 0; s < FR_CH; ++s) {
+            const int ks = k + s * 32;
+#pragma unroll
+            for (int j = 0; j < MT; ++j)
+#pragma unroll
+                for (int h = 0; h < (A_F32 ? 2 : 1); ++h) b.a[s][j][h] = z;
+#pragma unroll
+            for (int i = 0; i < NTL; ++i) b.w[s][i] = z;
+            if (ks + 8 * fg < ke) {
+#pragma unroll
+                for (int j = 0; j < MT; ++j)
+#pragma unroll
+                    for (int h = 0; h < (A_F32 ? 2 : 1); ++h) b.a[s][j][h] = *(const u32x4*)(ap[j] + (long)ks * (A_F32 ? 4 : 2) + 16 * h);
+#pragma unroll
+                for (int i = 0; i < NTL; ++i) b.w[s][i] = *(const u32x4*)(wp[i] + ks);
             }
         }
+    };
+    auto mma = [&](const Buf& b, int k) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < FR_CH; ++s) {
+            if (k + s * 32 >= ke) break;                      // (wave-uniform)
+            bf16x8 xf[MT];
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < MT; ++j) {
+                if (A_F32) xf[j] = cvt8(*(const float4*)&b.a[s][j][0], *(const float4*)&b.a[s][j][A_F32 ? 1 : 0]);
+                else xf[j] = *(const bf16x8*)&b.a[s][j][0];
+            }
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = mfma16(*(const bf16x8*)&wa[s][i], *(const bf16x8*)&xa[s][j], acc[i][j]);
+            for (int i = 0; i < NTL; ++i)
+#pragma unroll
+                for (int j = 0; j < MT; ++j) acc[i][j] = mfma16(*(const bf16x8*)&b.w[s][i], xf[j], acc[i][j]);
+        }
+    };
+    Buf b0, b1;
+    load(b0, kb);
+    for (int k = kb; k < ke; k += 2 * FR_CH * 32) {
+        load(b1, k + FR_CH * 32);
+        mma(b0, k);
+        load(b0, k + 2 * FR_CH * 32);
+        mma(b1, k + FR_CH * 32);
     }
-    // acc[i][j][r] = C[m = j*16 + fr][n = i*16 + 4*fg + r]
-    float* mine = part + wave * 64 * LDP;
+    // acc[i][j][r] = C[m = mw + j*16 + fr][n = nw + i*16 + 4*fg + r]
+    float* mine = NR == 4 ? part + wave * TM * LDP : part + wm * WM * LDP + wn * WN;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < MT; ++j)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *(f32x4*)(mine + (j * 16 + fr) * LDP + i * 16 + 4 * fg) = acc[i][j];
+        for (int i = 0; i < NTL; ++i) *(f32x4*)(mine + (j * 16 + fr) * LDP + i * 16 + 4 * fg) = acc[i][j];
     __syncthreads();
-    const int row = t >> 2, m = m0 + row;
-    if (m >= p.M) return;
+    constexpr int CG = TN / 8, ITEMS = TM * CG;               // a thread owns 8 consecutive columns of a row
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int c = (t & 3) * 16 + h * 8, n = n0 + c;
-        if (n >= p.N) continue;
-        const bool full8 = (n + 8 <= p.N);
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < (ITEMS + 255) / 256; ++it) {
+        const int idx = it * 256 + t;
+        const int row = idx / CG, c = (idx - row * CG) * 8;
+        const int m = m0 + row, n = n0 + c;
+        if (idx >= ITEMS || m >= p.M || n >= p.N) continue;
+        const bool full8 = (n + 8 <= p.N);                    // N % 4 == 0: either 8 or 4 valid columns
+        float v[8];
+        if (NR == 1) {
+            const f32x4 a0 = *(const f32x4*)(part + row * LDP + c), a1 = *(const f32x4*)(part + row * LDP + c + 4);
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const f32x4 a0 = *(const f32x4*)(part + (w * 64 + row) * LDP + c), a1 = *(const f32x4*)(part + (w * 64 + row) * LDP + c + 4);
+            for (int r = 0; r < 4; ++r) { v[r] = a0[r]; v[4 + r] = a1[r]; }
+        } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { v[r] += a0[r]; v[4 + r] += a1[r]; }
+            for (int r = 0; r < 8; ++r) v[r] = 0.f;
+#pragma unroll
+            for (int w = 0; w < NR; ++w) {
+                const f32x4 a0 = *(const f32x4*)(part + (w * TM + row) * LDP + c), a1 = *(const f32x4*)(part + (w * TM + row) * LDP + c + 4);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { v[r] += a0[r]; v[4 + r] += a1[r]; }
+            }
         }
         if (p.bias != nullptr) {
             const float4 b0 = *(const float4*)(p.bias + n);
             v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
             if (full8) { const float4 b1 = *(const float4*)(p.bias + n + 4); v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w; }
-        }
+        } else if (NR == 1) {                                 // (gemm_nt_kernel adds a zero bias: -0 becomes +0)
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] *= nt_alpha(p, m);
+            for (int r = 0; r < 8; ++r) v[r] += 0.f;
+        }
+        const float al = nt_alpha(p, m);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = mul_rounded(v[r], al);
         epilogue8<EPI, OUT_F32>(p, m, n, full8, v);
     }
 }
@@ -1184,7 +1244,7 @@ static int launch_nt256(GemmNT& p, hipStream_t stream) {
     return UENC_OK;
 }
 
-// The two small-shape kernels (register-staged 128 x 128 tiles; K-split 64 x 64 tiles): no dynamic LDS, nothing to set up.
+// The two small-shape kernels (register-staged 128 x 128 tiles; the few-row kernel): no dynamic LDS, nothing to set up.
 template <int EPI, int OUT_F32>
 static int launch_nt_tile128(GemmNT& p, int batch, hipStream_t stream) {
     p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
@@ -1192,13 +1252,30 @@ static int launch_nt_tile128(GemmNT& p, int batch, hipStream_t stream) {
     return UENC_OK;
 }
 
-template <int EPI, int OUT_F32>
-static int launch_nt_skinny(GemmNT& p, hipStream_t stream) {
-    p.tiles_m = (p.M + 63) / 64; p.tiles_n = (p.N + 63) / 64;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(GEMM_THREADS);
-    if (p.a_f32) hipLaunchKernelGGL((gemm_nt_skinny_kernel<EPI, OUT_F32, 1>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((gemm_nt_skinny_kernel<EPI, OUT_F32, 0>), grid, block, 0, stream, p);
+// The few-row kernel.  nr == 4 (the shapes with four summed k-ranges): a 16 x 32 tile, or 32 x 32 where that still puts half of the
+// CUs to work.  nr == 1: 64 x 64 (2 x 2 waves of 32 x 32).
+template <int EPI, int OUT_F32, int A_F32>
+static int launch_nt_fewrow_a(GemmNT& p, int nr, hipStream_t stream) {
+    const dim3 block(GEMM_THREADS);
+    if (nr == 1) {
+        p.tiles_m = (p.M + 63) / 64; p.tiles_n = (p.N + 63) / 64;
+        hipLaunchKernelGGL((gemm_nt_fewrow_kernel<EPI, OUT_F32, A_F32, 1, 2, 2>), dim3(p.tiles_m * p.tiles_n), block, 0, stream, p);
+        return UENC_OK;
+    }
+    p.tiles_n = (p.N + 31) / 32;
+    if ((long)((p.M + 31) / 32) * p.tiles_n * 2 >= nt_cu_count()) {
+        p.tiles_m = (p.M + 31) / 32;
+        hipLaunchKernelGGL((gemm_nt_fewrow_kernel<EPI, OUT_F32, A_F32, 4, 2, 2>), dim3(p.tiles_m * p.tiles_n), block, 0, stream, p);
+    } else {
+        p.tiles_m = (p.M + 15) / 16;
+        hipLaunchKernelGGL((gemm_nt_fewrow_kernel<EPI, OUT_F32, A_F32, 4, 1, 2>), dim3(p.tiles_m * p.tiles_n), block, 0, stream, p);
+    }
     return UENC_OK;
+}
+
+template <int EPI, int OUT_F32>
+static int launch_nt_fewrow(GemmNT& p, int nr, hipStream_t stream) {
+    return p.a_f32 ? launch_nt_fewrow_a<EPI, OUT_F32, 1>(p, nr, stream) : launch_nt_fewrow_a<EPI, OUT_F32, 0>(p, nr, stream);
 }
 
 // 256 x 192 or 256 x 256 tiles?  Rounds of tiles over the CUs x cost per tile.  Measured (tools/gemm_nt192_ab.py ->
@@ -1226,7 +1303,7 @@ static bool nt128_wins(int M, int N, int K, int c_dtype) {
 // The kernel that takes a shape.  Legality first; where two LDS-DMA kernels are legal the measured choosers above decide, or the
 // caller's `tile` (UENC_NT_TILE_*: the tests and the A/B tools pin a kernel with it).  `tile` replaces the choosers' answer only: a
 // shape the named kernel does not take is refused, never sent elsewhere.  summed = split-K / accumulate (fp32 atomics) or stored partials.
-enum NtRoute { NT_REFUSED = -1, NT_TILE128, NT_SKINNY, NT_HALF, NT_256, NT_192 };
+enum NtRoute { NT_REFUSED = -1, NT_TILE128, NT_FEWROW4, NT_FEWROW1, NT_HALF, NT_256, NT_192 };
 
 static NtRoute nt_route(int M, int N, int K, int batch, int a_dtype, long lda, int c_dtype, int epilogue, bool summed, int klen, int splitk,
                         bool ln, int tile) {
@@ -1248,9 +1325,18 @@ static NtRoute nt_route(int M, int N, int K, int batch, int a_dtype, long lda, i
                      (c_dtype == UENC_F32 ? (epilogue == EPI_NONE || epilogue == EPI_RESIDUAL || epilogue == EPI_RELU) : true);
     if (tile != 0 && !big) return NT_REFUSED;
     if (ln && !(big || mid)) return NT_REFUSED;       // (the small-shape kernels have no row-wide epilogue: the caller runs LayerNorm itself)
-    // few output tiles (the decoder's M = 300-row GEMMs): the K-split 64 x 64 kernel
+    // few output tiles (the decoder's M = 300-row GEMMs): the few-row kernel, four k-ranges summed in order
     const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if (!big && batch == 1 && !summed && tiles128 <= 32 && K >= 64) return NT_SKINNY;
+    const bool few = !big && !mid && batch == 1 && !summed && K >= 64;
+    if (!big && batch == 1 && !summed && tiles128 <= 32 && K >= 64) return NT_FEWROW4;
+    // the same kernel as one chain per element (the sums of the 128 x 128 kernel), where it was measured faster than that kernel
+    // (tools/gemm_fewrow_bench.py -> profiles/gemm_fewrow_bench.json), both at K = 256: any width at M <= 320 (300 x 2048 x 256: 160
+    // workgroups of 64 x 64 instead of 48 of 128 x 128, -7 %), and the decoder's key / value projection of the smallest map (4096 x 256 x
+    // 256: 256 workgroups instead of 64, -5 ... -20 %).  Longer contractions were not measured and stay where they were.
+    // Not the residual epilogue: the 128 x 128 kernel's compiled epilogue contracts the alpha product into the residual add for the first
+    // four of a thread's eight columns only, and no step shape needs that reproduced here.
+    const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
+    if (few && epilogue != EPI_RESIDUAL && K <= 256 && (M <= 320 || (N == 256 && K == 256 && tiles64 <= nt_cu_count()))) return NT_FEWROW1;
     if (!(big || mid)) return NT_TILE128;
     if (mid || (!summed && (K % BK3 == 0) && prefer_half)) return NT_HALF;
     if (tile == UENC_NT_TILE_128X256) return NT_REFUSED;
@@ -1270,7 +1356,7 @@ static int launch_nt(NtRoute route, GemmNT& p, int batch, hipStream_t stream) {
         default: break;
     }
     if constexpr (EPI != EPI_RESIDUAL || OUT_F32) {
-        if (route == NT_SKINNY) return launch_nt_skinny<EPI, OUT_F32>(p, stream);
+        if (route == NT_FEWROW4 || route == NT_FEWROW1) return launch_nt_fewrow<EPI, OUT_F32>(p, route == NT_FEWROW4 ? 4 : 1, stream);
         if (route == NT_TILE128) return launch_nt_tile128<EPI, OUT_F32>(p, batch, stream);
     }
     return UENC_EINVAL;
