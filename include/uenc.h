@@ -107,6 +107,15 @@ int uenc_groupnorm_tokens_bwd(const void* dy, int dy_dtype, const void* x, int x
 /* adjoint of the bilinear merge: dsrc (B, Hs, Ws, C) fp32 overwritten from dy (B, H, W, C) fp32|bf16, H >= Hs, W >= Ws. */
 int uenc_upsample_bilinear_tokens_bwd(const void* dy, int dy_dtype, float* dsrc, int B, int H, int W, int Hs, int Ws, int C,
                                       uenc_stream_t stream);
+/* Nearest-neighbour top-down merge of the plain FPN decoders (csrc/fpn_nearest.hip; reference pixel_decoder/fpn.py:151, :304):
+ * out (B, H, W, C) = a (B, H, W, C) + prev (B, Hs, Ws, C)[nearest], every tensor fp32|bf16, the sum taken in fp32; source index
+ * min((int)floorf(dst * ((float)Hs / H)), Hs - 1) as F.interpolate(mode="nearest").  C % 4 == 0; fp32 tensors 16-byte, bf16 8-byte
+ * aligned.  Adjoint: dprev (B, Hs, Ws, C) fp32, every element written = the fp32 sum, in row-major order of the destination, of the
+ * dy pixels whose forward index is that pixel (a gather, no atomics); any size ratio. */
+int uenc_merge_nearest_tokens_fwd(const void* a, int a_dtype, const void* prev, int prev_dtype, void* out, int out_dtype, int B, int H, int W,
+                                  int Hs, int Ws, int C, uenc_stream_t stream);
+int uenc_merge_nearest_tokens_bwd(const void* dy, int dy_dtype, float* dprev, int B, int H, int W, int Hs, int Ws, int C,
+                                  uenc_stream_t stream);
 /* 3x3 / stride 1 / pad 1 convolution as a GEMM (bf16, C % 8 == 0): col (B*H*W, 9*C) with column (ky, kx, c) from
  * in (B, H, W, C), and the adjoint dx (B, H, W, C) from dcol (B*H*W, 9*C). */
 int uenc_im2col3x3(const void* in, void* col, int B, int H, int W, int C, uenc_stream_t stream);
@@ -432,6 +441,33 @@ int uenc_mha_bwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_b
                     const float* lse, const void* dout, long do_bs, long do_rs, float* dq, long dq_bs, long dq_rs, void* dk,
                     long dk_bs, long dk_rs, void* dv, long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale,
                     float dropout_p, const unsigned* seeds, int slot, uenc_stream_t stream);
+
+/* ---- query-tiled attention core (csrc/attn_tiled.hip): a whole feature map attending to itself (the DETR encoder of
+ * TransformerEncoderPixelDecoder, reference modeling/pixel_decoder/fpn.py:155-232 on transformer.py:161-234) ---------------------------
+ * Tensor contract of uenc_mha_fwd / uenc_mha_bwd without mask and workspace, head_dim 32, any Lq >= 1 and S >= 1 (the query count is
+ * bounded by the grid alone: ceil(Lq / 64) * B * H and ceil(S / 64) * B * H below 2^31).  q, k, v, out, dout: bf16, row / batch
+ * strides multiples of 8 elements and 16-byte aligned pointers (out in the forward: multiples of 4, 8-byte aligned); lse (B, H, Lq)
+ * fp32, log2 domain.  Dropout as uenc_mha_fwd: element index ((b H + h) Lq + q) S + key.
+ * Backward: dq (B, Lq, *) fp32 WRITTEN (strides multiples of 4, 16-byte aligned), dk, dv (B, S, *) bf16 written (strides multiples
+ * of 4, 8-byte aligned).  Two kernels (dQ per query tile, dK / dV per key tile), no atomics, nothing to zero: the same input gives
+ * the same bits.  uenc_attn_tiled_tile(0) = queries per workgroup, (1) = keys per LDS block / per dK-dV workgroup. */
+int uenc_attn_tiled_tile(int which);
+int uenc_attn_tiled_fwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                        long v_rs, void* out, long o_bs, long o_rs, float* lse, int B, int H, int Lq, int S, float scale,
+                        float dropout_p, unsigned seed, uenc_stream_t stream);
+int uenc_attn_tiled_bwd(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                        long v_rs, const void* out, long o_bs, long o_rs, const float* lse, const void* dout, long do_bs,
+                        long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs, long dk_rs, void* dv, long dv_bs,
+                        long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p, unsigned seed,
+                        uenc_stream_t stream);
+int uenc_attn_tiled_fwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                           long v_rs, void* out, long o_bs, long o_rs, float* lse, int B, int H, int Lq, int S, float scale,
+                           float dropout_p, const unsigned* seeds, int slot, uenc_stream_t stream);
+int uenc_attn_tiled_bwd_sp(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v, long v_bs,
+                           long v_rs, const void* out, long o_bs, long o_rs, const float* lse, const void* dout, long do_bs,
+                           long do_rs, float* dq, long dq_bs, long dq_rs, void* dk, long dk_bs, long dk_rs, void* dv,
+                           long dv_bs, long dv_rs, int B, int H, int Lq, int S, float scale, float dropout_p,
+                           const unsigned* seeds, int slot, uenc_stream_t stream);
 
 /* ---- fused AdamW with full-model gradient clipping (csrc/optim.hip; replaces the reference's optimizer wrapper, tools/calc_throughput.py:
  * torch.nan_to_num on every gradient, clip_grad_norm_ over all of them, torch.optim.AdamW) ------------------------------------------------

@@ -19,6 +19,8 @@ from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55
 _sys.modules[__name__ + ".modeling"] = modeling
 _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
+_sys.modules[__name__ + ".modeling.pixel_decoder"] = modeling.pixel_decoder
+_sys.modules[__name__ + ".modeling.pixel_decoder.fpn"] = modeling.pixel_decoder.fpn
 _sys.modules[__name__ + ".modeling.backbone"] = modeling.backbone
 _sys.modules[__name__ + ".modeling.backbone.convnext"] = modeling.backbone.convnext
 _sys.modules[__name__ + ".modeling.backbone.resnet"] = modeling.backbone.resnet

@@ -112,6 +112,70 @@ def mha(q, k, v, nheads: int, mask: Optional[torch.Tensor] = None, dropout_p: fl
     return MHACoreFn.apply(q, k, v, nheads, mask, dropout_p, seed)
 
 
+class AttnTiledFn(torch.autograd.Function):
+    """The unmasked core on the query-tiled kernels of csrc/attn_tiled.hip: any Lq and S (a whole feature map attending to itself).
+    Same tensor contract, dropout hash and rounding points as MHACoreFn; the backward writes dq (no zeroing, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nheads, dropout_p=0.0, seed=0):
+        q, k, v = _strided(q), _strided(k), _strided(v)
+        B, Lq, E = q.shape
+        S = k.shape[1]
+        assert E == nheads * 32, "the HIP attention kernels are built for head_dim 32"
+        scale = 32 ** -0.5
+        lse = torch.empty((B, nheads, Lq), dtype=torch.float32, device=q.device)
+        sdp = lambda t: (t.data_ptr(), t.stride(0), t.stride(1))
+        if K.EXACT:                                      # fp32 operands, csrc/exact.hip (takes any Lq)
+            if isinstance(seed, K.SeedSlot):
+                raise RuntimeError("device-side dropout seeds (ops.device_rng) are not available in the fp32 exact mode")
+            out = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
+            check(lib.uenc_mha_f32_fwd(*sdp(q), *sdp(k), *sdp(v), 0, 0, *sdp(out), lse.data_ptr(), B, nheads, Lq, S, scale,
+                                       float(dropout_p), int(seed), stream_ptr()), "mha_f32_fwd")
+        else:
+            out = torch.empty((B, Lq, E), dtype=torch.bfloat16, device=q.device)
+            args = (*sdp(q), *sdp(k), *sdp(v), *sdp(out), lse.data_ptr(), B, nheads, Lq, S, scale, float(dropout_p))
+            if isinstance(seed, K.SeedSlot):             # seed read on the device (capturable step, ops.device_rng)
+                check(lib.uenc_attn_tiled_fwd_sp(*args, seed.seeds.data_ptr(), seed.slot, stream_ptr()), "attn_tiled_fwd_sp")
+            else:
+                check(lib.uenc_attn_tiled_fwd(*args, int(seed), stream_ptr()), "attn_tiled_fwd")
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.meta = (nheads, S, scale, float(dropout_p), seed if isinstance(seed, K.SeedSlot) else int(seed))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        nheads, S, scale, dropout_p, seed = ctx.meta
+        B, Lq, E = q.shape
+        dout = _strided(dout)
+        sdp = lambda t: (t.data_ptr(), t.stride(0), t.stride(1))
+        dq = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
+        if K.EXACT:
+            dk = torch.zeros((B, S, E), dtype=torch.float32, device=q.device)
+            dv = torch.zeros((B, S, E), dtype=torch.float32, device=q.device)
+            delta = torch.empty((B, nheads, Lq), dtype=torch.float32, device=q.device)
+            check(lib.uenc_mha_f32_bwd(*sdp(q), *sdp(k), *sdp(v), 0, 0, *sdp(out), lse.data_ptr(), *sdp(dout), *sdp(dq), *sdp(dk), *sdp(dv),
+                                       delta.data_ptr(), B, nheads, Lq, S, scale, dropout_p, seed, stream_ptr()), "mha_f32_bwd")
+            return dq, dk, dv, None, None, None
+        dk = torch.empty((B, S, E), dtype=torch.bfloat16, device=q.device)
+        dv = torch.empty((B, S, E), dtype=torch.bfloat16, device=q.device)
+        args = (*sdp(q), *sdp(k), *sdp(v), *sdp(out), lse.data_ptr(), *sdp(dout), *sdp(dq), *sdp(dk), *sdp(dv), B, nheads, Lq, S, scale,
+                dropout_p)
+        if isinstance(seed, K.SeedSlot):
+            seed.check()
+            check(lib.uenc_attn_tiled_bwd_sp(*args, seed.seeds.data_ptr(), seed.slot, stream_ptr()), "attn_tiled_bwd_sp")
+        else:
+            check(lib.uenc_attn_tiled_bwd(*args, seed, stream_ptr()), "attn_tiled_bwd")
+        return dq.to(torch.bfloat16), dk, dv, None, None, None
+
+
+def mha_tiled(q, k, v, nheads: int, dropout_p: float = 0.0, seed: int = 0):
+    """softmax(q k^T / sqrt(32)) v without a mask, for any number of queries and keys (csrc/attn_tiled.hip)."""
+    if not q.is_cuda:
+        raise RuntimeError("uenc attention runs on the GPU only")
+    return AttnTiledFn.apply(q, k, v, nheads, dropout_p, seed)
+
+
 def keep_mask_reference(B: int, nheads: int, Lq: int, S: int, dropout_p: float, seed: int) -> torch.Tensor:
     """(B, nheads, Lq, S) bool: the keep-mask the kernels derive (common.h attn_keep), restated with int64 torch arithmetic on the
     host.  Test helper: lets a dense PyTorch attention reproduce a dropped-out kernel result exactly."""

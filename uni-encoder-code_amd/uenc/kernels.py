@@ -907,6 +907,27 @@ def upsample_bilinear_tokens_bwd(dy, Hs: int, Ws: int):
     return out
 
 
+def merge_nearest_tokens_fwd(a, prev, hw, out_dtype=torch.float32):
+    """a (B, H*W, C) + nearest-resized prev (B, Hs, Ws, C) -> (B, H*W, C) out_dtype; fp32|bf16 operands, the sum in fp32."""
+    B, HW, C = a.shape
+    H, W = hw
+    assert a.is_cuda and a.is_contiguous() and prev.is_contiguous() and HW == H * W and prev.shape[0] == B and prev.shape[3] == C
+    out = torch.empty((B, HW, C), dtype=_odt(out_dtype), device=a.device)
+    check(lib.uenc_merge_nearest_tokens_fwd(a.data_ptr(), dt(a), prev.data_ptr(), dt(prev), out.data_ptr(), dt(out), B, H, W,
+                                            prev.shape[1], prev.shape[2], C, stream_ptr()), "merge_nearest_tokens_fwd")
+    return out
+
+
+def merge_nearest_tokens_bwd(dy, Hs: int, Ws: int):
+    """dy (B, H, W, C) fp32|bf16 -> (B, Hs, Ws, C) fp32: adjoint of the nearest resize (Hs, Ws) -> (H, W)."""
+    B, H, W, C = dy.shape
+    assert dy.is_contiguous()
+    out = torch.empty((B, Hs, Ws, C), dtype=torch.float32, device=dy.device)
+    check(lib.uenc_merge_nearest_tokens_bwd(dy.data_ptr(), dt(dy), out.data_ptr(), B, H, W, Hs, Ws, C, stream_ptr()),
+          "merge_nearest_tokens_bwd")
+    return out
+
+
 def im2col3x3(x16):
     """(B, H, W, C) bf16 -> (B*H*W, 9*C) bf16 patch matrix, column order (ky, kx, c)."""
     B, H, W, C = x16.shape

@@ -3,8 +3,9 @@
 Same registry name, `from_config` keys and `forward(seg_features, depth_features, tasks, mask=None)
 -> (predictions_seg, predictions_depth)` contract.  The depth decoder (`TransDSSL`, sequence branch)
  is built, like in the reference (:112), from `MODEL.SEM_SEG_HEAD.DEPTH_DECODER_NAME` whenever a class of
-that name is registered (uenc/modeling/pixel_decoder/transdssl.py registers `TransDSSL`); otherwise `depth_decoder` is None and
-depth features are rejected loudly.
+that name is registered (uenc/modeling/pixel_decoder/transdssl.py registers `TransDSSL`) and predicts depth; otherwise -- the key's
+default "BasePixelDecoder" included: the segmentation pixel decoders of pixel_decoder/fpn.py return mask features, not depth, and
+declare `predicts_depth = False` -- `depth_decoder` is None and depth features are rejected loudly.
 """
 import logging
 from typing import Dict
@@ -56,7 +57,10 @@ class OneFormerHead(nn.Module):
         else:
             in_ch = input_shape[tif].channels
         depth_name = cfg.MODEL.SEM_SEG_HEAD.DEPTH_DECODER_NAME
-        depth_decoder = build_pixel_decoder(cfg, input_shape, depth_decoder=True) if depth_name in SEM_SEG_HEADS_REGISTRY else None
+        depth_cls = SEM_SEG_HEADS_REGISTRY.get(depth_name) if depth_name in SEM_SEG_HEADS_REGISTRY else None
+        depth_decoder = None
+        if depth_cls is not None and getattr(depth_cls, "predicts_depth", True):
+            depth_decoder = build_pixel_decoder(cfg, input_shape, depth_decoder=True)
         return {
             "input_shape": {k: v for k, v in input_shape.items() if k in cfg.MODEL.SEM_SEG_HEAD.IN_FEATURES},
             "ignore_value": cfg.MODEL.SEM_SEG_HEAD.IGNORE_VALUE,

@@ -45,9 +45,10 @@ class MultiheadAttention(nn.Module):
     shared by all heads (the reference repeats one mask over heads, oneformer_transformer_decoder.py:510).
     """
 
-    def __init__(self, embed_dim, num_heads, dropout=0.0):
+    def __init__(self, embed_dim, num_heads, dropout=0.0, tiled=False):
         super().__init__()
         self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.tiled = bool(tiled)                # unmasked core on the query-tiled kernels (any Lq: a feature map attending to itself)
         self.dropout = float(dropout)           # on the attention probabilities, training mode only (nn.MultiheadAttention semantics)
         self.last_seed = None                   # seed of the last training forward (tests rebuild the keep-mask from it)
         self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
@@ -65,7 +66,15 @@ class MultiheadAttention(nn.Module):
             q = ops.linear(query, W, b, rows=(0, E))
             k = ops.linear(key, W, b, rows=(E, 2 * E))
         v = ops.linear(value, W, b, rows=(2 * E, 3 * E))
-        if self.training and self.dropout > 0.0:
+        if self.tiled:
+            if attn_mask is not None:
+                raise NotImplementedError("the query-tiled attention core takes no mask")
+            if self.training and self.dropout > 0.0:
+                self.last_seed = ops.dropout_seed()
+                o = ops.attention_tiled(q, k, v, self.num_heads, self.dropout, self.last_seed)
+            else:
+                o = ops.attention_tiled(q, k, v, self.num_heads)
+        elif self.training and self.dropout > 0.0:
             self.last_seed = ops.dropout_seed()      # torch's CPU generator: no device sync (device-RNG mode: a device seed slot)
             o = ops.attention(q, k, v, self.num_heads, attn_mask, self.dropout, self.last_seed)
         else:
@@ -174,6 +183,40 @@ class TransformerDecoderLayer(nn.Module):
         return _ln(self.norm3, h)
 
 
+class TransformerEncoderLayer(nn.Module):
+    """Post-norm DETR encoder layer (reference transformer.py:161-234, forward_post :196-214) over a whole feature map: self-attention
+    with q = k = src + pos, v = src on the query-tiled attention core (csrc/attn_tiled.hip), then the FFN.  Batch-first (B, L, E)."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu", normalize_before=False):
+        super().__init__()
+        if normalize_before:
+            raise NotImplementedError("MODEL.ONE_FORMER.PRE_NORM True (pre-norm encoder layers, transformer.py:216-234) is not implemented: "
+                                      "every shipped config has MODEL.ONE_FORMER.PRE_NORM False")
+        assert activation == "relu"
+        self.self_attn = MultiheadAttention(d_model, nhead, dropout=dropout, tiled=True)
+        self.linear1 = nn.Linear(d_model, dim_feedforward)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        self.norm1, self.norm2 = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+        self.dropout_p = float(dropout)         # dropout, dropout1 / 2 of the reference (transformer.py:177-181), training only
+        self._masks = []                        # keep-masks of the last training forward, in order: dropout1, FFN inner, dropout2 (tests)
+
+    _drop = TransformerDecoderLayer._drop
+
+    def forward(self, src, pos=None):
+        qk = src if pos is None else src + pos
+        if self.training and self.dropout_p > 0.0:
+            # training: the residual / FFN fusions are split where the reference applies dropout1 / 2 and the FFN's inner dropout
+            # (transformer.py:207-213); the attention-probability dropout runs inside the attention kernels
+            self._masks = []
+            src = _ln(self.norm1, src + self._drop(self.self_attn(qk, qk, src)))
+            h = self._drop(F.relu(ops.linear(src, self.linear1.weight, self.linear1.bias, out_dtype=torch.float32)))
+            h = ops.linear(h, self.linear2.weight, self.linear2.bias, out_dtype=torch.float32)
+            return _ln(self.norm2, src + self._drop(h))
+        src = _ln(self.norm1, self.self_attn(qk, qk, src, residual=src))
+        h = ops.mlp(src, [self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias], act="relu", residual=src)
+        return _ln(self.norm2, h)
+
+
 class TransformerDecoder(nn.Module):
     def __init__(self, layer_args, num_layers, norm=None):
         super().__init__()
@@ -182,12 +225,20 @@ class TransformerDecoder(nn.Module):
 
 
 class TransformerEncoder(nn.Module):
-    def __init__(self, num_layers, norm=None):
+    """`layers` of TransformerEncoderLayer (+ `norm`).  The class transformer passes no `layer_args` and has none (ENC_LAYERS 0); the
+    pixel decoder's TransformerEncoderOnly builds its layers here (reference transformer.py:85-111)."""
+
+    def __init__(self, num_layers, norm=None, layer_args=None):
         super().__init__()
-        if num_layers != 0:
+        if num_layers != 0 and layer_args is None:
             raise NotImplementedError("ENC_LAYERS is 0 in every shipped config (oneformer_R50_bs16_90k.yaml:33)")
-        self.layers = nn.ModuleList()
+        self.layers = nn.ModuleList([TransformerEncoderLayer(*layer_args) for _ in range(num_layers)])
         self.num_layers, self.norm = num_layers, norm
+
+    def forward(self, src, pos=None):
+        for layer in self.layers:
+            src = layer(src, pos)
+        return src if self.norm is None else _ln(self.norm, src)
 
 
 class Transformer(nn.Module):

@@ -1471,6 +1471,13 @@ def attention(q, k, v, nheads: int, mask: Optional[torch.Tensor] = None, dropout
     return mha(q, k, v, nheads, mask, dropout_p, seed)
 
 
+def attention_tiled(q, k, v, nheads: int, dropout_p: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """The same core without a mask for ANY number of queries and keys (a feature map attending to itself: csrc/attn_tiled.hip, query-tiled
+    forward, dQ per query tile, dK / dV per key tile).  -> (B, Lq, E) bf16 (fp32 in exact mode, through uenc_mha_f32_*)."""
+    from .attention import mha_tiled
+    return mha_tiled(q, k, v, nheads, dropout_p, seed)
+
+
 # --------------------------------------------------------------------------------------------
 # 3x3 convolution (stride 1, pad 1, no bias) on channels-last maps as im2col + MFMA GEMM
 # --------------------------------------------------------------------------------------------
@@ -1569,19 +1576,19 @@ class Conv3x3Fn(torch.autograd.Function):
             K.gemm_tn(dy2, col, dw, None)
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, bias=None):
         B, H, W, C = x.shape
         x16 = x if x.dtype == K.adt() else x.to(K.adt())
         col = K.im2col3x3(x16 if x16.is_contiguous() else x16.contiguous())
-        out = K.gemm_nt(col, _conv_wmat(weight, "c3"), out_dtype=F32)
-        ctx.save_for_backward(col, weight)
+        out = K.gemm_nt(col, _conv_wmat(weight, "c3"), bias=None if bias is None else bias.detach(), out_dtype=F32)
+        ctx.save_for_backward(col, weight, bias)
         ctx.shape = (B, H, W, C)
         ctx.in_dtype = x.dtype
         return out.view(B, H * W, weight.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        col, weight = ctx.saved_tensors
+        col, weight, bias = ctx.saved_tensors
         B, H, W, C = ctx.shape
         dy2 = _conv_dy(dy, B * H * W, weight.shape[0])
         dx = None
@@ -1590,13 +1597,14 @@ class Conv3x3Fn(torch.autograd.Function):
             dx = K.col2im3x3(dcol, B, H, W, C)
             dx = dx if dx.dtype == ctx.in_dtype else dx.to(ctx.in_dtype)
         if weight.requires_grad:
-            _conv_wgrad(dy2, col, weight, None, Conv3x3Fn._wgrad_gemm)
-        return dx, None
+            # (a biased conv takes the plain TN GEMM, whose epilogue also forms the column sums of dy = the bias gradient)
+            _conv_wgrad(dy2, col, weight, bias, Conv3x3Fn._wgrad_gemm if bias is None else None)
+        return dx, None, None
 
 
-def conv3x3(x_nhwc, weight):
-    """x (B, H, W, Cin) bf16|fp32 channels-last -> (B, H*W, Cout) fp32."""
-    return Conv3x3Fn.apply(x_nhwc, weight)
+def conv3x3(x_nhwc, weight, bias=None):
+    """x (B, H, W, Cin) bf16|fp32 channels-last -> (B, H*W, Cout) fp32; bias (Cout) through the GEMM's bias epilogue."""
+    return Conv3x3Fn.apply(x_nhwc, weight, bias)
 
 
 class _SubCtx:
@@ -1675,8 +1683,43 @@ class Conv3x3GroupNormFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
-def linear_group_norm(x, conv, gn, *, relu=False, add_src=None, add_hw=None, out_dtype=F32):
-    """conv: a 1x1 Conv2d / Linear (weight, bias); gn: nn.GroupNorm.  -> (B, HW, C)."""
+class MergeNearestFn(torch.autograd.Function):
+    """a (B, HW, C) + nearest-resized prev (B, Hs, Ws, C) -> (B, HW, C): the top-down merge of the plain FPN decoders (reference
+    pixel_decoder/fpn.py:151, :304; csrc/fpn_nearest.hip).  The gradient of `a` is the incoming one; that of `prev` is the gather adjoint."""
+
+    @staticmethod
+    def forward(ctx, a, prev, hw, out_dtype):
+        ctx.cfg = (tuple(prev.shape), hw, a.dtype, prev.dtype)
+        return K.merge_nearest_tokens_fwd(a if a.is_contiguous() else a.contiguous(), prev if prev.is_contiguous() else prev.contiguous(),
+                                          hw, out_dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (B, Hs, Ws, C), (H, W), adt, pdt = ctx.cfg
+        da = dp = None
+        if ctx.needs_input_grad[0]:
+            da = dy if dy.dtype == adt else dy.to(adt)
+        if ctx.needs_input_grad[1]:
+            dyc = dy if dy.is_contiguous() else dy.contiguous()
+            dp = K.merge_nearest_tokens_bwd(dyc.view(B, H, W, C), Hs, Ws)
+            dp = dp if dp.dtype == pdt else dp.to(pdt)
+        return da, dp, None, None
+
+
+def merge_nearest(a_tok, prev_nhwc, hw, *, out_dtype=F32):
+    """a (B, H*W, C) + F.interpolate(prev, size=hw, mode="nearest") on channels-last maps; prev (B, Hs, Ws, C)."""
+    return MergeNearestFn.apply(a_tok, prev_nhwc, tuple(hw), out_dtype)
+
+
+def linear_group_norm(x, conv, gn, *, relu=False, add_src=None, add_hw=None, out_dtype=F32, merge="bilinear"):
+    """conv: a 1x1 Conv2d / Linear (weight, bias); gn: nn.GroupNorm.  -> (B, HW, C).  merge: how add_src is resized to add_hw --
+    "bilinear" inside the GroupNorm pass (the MSDeformAttn decoder), "nearest" by the stand-alone merge kernel behind it (the plain
+    FPN decoders)."""
+    if merge == "nearest" and add_src is not None:
+        assert not relu
+        y = LinearGroupNormFn.apply(x, conv.weight, conv.bias, gn.weight, gn.bias, gn.num_groups, gn.eps, False, None, None, F32)
+        return merge_nearest(y, add_src, add_hw, out_dtype=out_dtype)
+    assert merge in ("bilinear", "nearest")
     return LinearGroupNormFn.apply(x, conv.weight, conv.bias, gn.weight, gn.bias, gn.num_groups, gn.eps, relu, add_src, add_hw, out_dtype)
 
 
