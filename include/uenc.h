@@ -514,6 +514,41 @@ int uenc_match_cost(const void* probs, int n_prob, int Q, int C1, int h, int w, 
  * read as 100 and entries are clamped to +-1e30, so the search always terminates.  Limits: 1 <= Q <= 256, 0 <= T <= 256, ld >= T. */
 int uenc_lsap_solve(const void* probs, int n_prob, int Q, uenc_stream_t stream);
 
+/* ---- set criterion (csrc/criterion.hip; uenc.modeling.criterion.SetCriterion) ---------------------------------------------------------------
+ * Point-sampled mask and dice losses of the matched pairs and the weighted class loss, ALL prediction heads per call, fp32, no float
+ * atomics: the same input gives the same bits.  A pair is one matched (query, target) of one image of one head; a head's pairs run over the
+ * images in order, within an image in the matcher's order, N = sum_b min(Q, T_b) per head, and row r = head * N + n of every buffer is
+ * pair n of that head.  row_ind / col_ind are the matcher's flat DEVICE index buffers (n_heads * N int64 each: the query and the target of
+ * every pair); a pair whose indices are out of range is inert (zero losses, no gradient).  `desc` is a HOST block of 1024 bytes which the
+ * call copies into its kernel arguments (a stream capture records the pointers by value):
+ *   {struct {const float* masks (bs, Q, h, w); const float* logits (bs, Q, C1);} head[16];
+ *    struct {const unsigned char* gt (T, Hg, Wg) 0 / 1; const int64* labels (T); int T; int pair0;} img[32];}
+ * with pair0 = the sum of min(Q, T) over the images before.  Limits: n_heads <= 16, bs <= 32, Q, T <= 256, maps up to 16384 x 16384,
+ * P, M <= 2^21.  Sampling is grid_sample at 2 p - 1 (bilinear, align_corners = False, zero padding), as in uenc_match_cost. */
+/* out (n_heads * N, M): the predicted logit map of every pair at its M points, points = (n_heads * N, M, 2) x, y in [0, 1]. */
+int uenc_crit_point_logits(const void* desc, int n_heads, int bs, int Q, int h, int w, int N, int M, const long long* row_ind,
+                           const float* points, float* out, uenc_stream_t stream);
+/* Per pair, x_p = logit map and t_p = target mask at point p of points (n_heads * N, P, 2):
+ *   loss[r] = {ce_n = (1 / P) sum_p bce_with_logits(x_p, t_p), dice_n = 1 - (2 sum s t + 1) / (sum s + sum t + 1)}, s = sigmoid(x);
+ *   sums[r] = {sum s t, sum s, sum t}.
+ * With unit and keys given (both or neither): unit (n_heads * N, P, 2) = {d ce_n / d x_p, d dice_n / d x_p} and keys (n_heads * N, P, 4)
+ * int32, 16-byte aligned = the cell y * w + x of the point's four taps (nw, ne, sw, se), h * w for a tap outside the map. */
+int uenc_crit_mask_loss_fwd(const void* desc, int n_heads, int bs, int Q, int h, int w, int Hg, int Wg, int N, int P, const long long* row_ind,
+                            const long long* col_ind, const float* points, float* loss, float* sums, float* unit, int* keys,
+                            uenc_stream_t stream);
+/* gmasks (n_heads, bs, Q, h, w), ZERO-FILLED by the caller: the gradient of sum_head (gce[head] sum_n ce_n + gdice[head] sum_n dice_n) *
+ * inv_num_masks to every head's mask logits.  sorted_keys / order (n_heads * N, 4 P) are a STABLE ascending sort of each row of `keys`
+ * and its permutation (int64); gce / gdice are n_heads device floats.  The lane at the head of each run of equal keys adds the run in
+ * sorted order and writes its cell once.  The queries of one image's pairs must be distinct, as those of an assignment are. */
+int uenc_crit_mask_loss_bwd(const void* desc, int n_heads, int bs, int Q, int h, int w, int N, int P, const long long* row_ind,
+                            const float* points, const float* unit, const int* sorted_keys, const long long* order, const float* gce,
+                            const float* gdice, float inv_num_masks, float* gmasks, uenc_stream_t stream);
+/* Per head: target class of row (b, q) = labels[col] of the image's pair whose query is q, else C1 - 1 (no object); weight 1, eos_coef for
+ * no object; loss[head] = sum w nll / sum w (F.cross_entropy with weights) and grad (n_heads, bs * Q, C1) = w (softmax - onehot) / sum w.
+ * rows = 2 * n_heads * bs * Q floats of workspace.  N may be 0 (no targets at all).  A label outside [0, C1) takes its row out of the loss. */
+int uenc_crit_class_loss(const void* desc, int n_heads, int bs, int Q, int C1, int N, const long long* row_ind, const long long* col_ind,
+                         float eos_coef, float* rows, float* loss, float* grad, uenc_stream_t stream);
+
 /* ---- MonodepthLoss hot path (csrc/monodepth.hip; reference model/modeling/monodepth_loss.py:427-517, 671-680, 734-777) ---------------------
  * fp32, dense tensors, S <= 4 scales (scale s is (H >> s) x (W >> s); H and W divisible by 2^(S-1)), NF <= 2 source frames, no float atomics:
  * the same input gives the same bits.  `desc` is a HOST block of 67 pointers which the call copies into its kernel arguments (a stream

@@ -18,6 +18,7 @@ from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55
 # product's modules: `from model.modeling.matcher import HungarianMatcher` gives `uenc.modeling.matcher.HungarianMatcher`.
 _sys.modules[__name__ + ".modeling"] = modeling
 _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
+_sys.modules[__name__ + ".modeling.criterion"] = modeling.criterion
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
 _sys.modules[__name__ + ".modeling.pixel_decoder"] = modeling.pixel_decoder
 _sys.modules[__name__ + ".modeling.pixel_decoder.fpn"] = modeling.pixel_decoder.fpn

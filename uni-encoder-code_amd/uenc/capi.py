@@ -121,6 +121,11 @@ _SIGNATURES = {
     "uenc_match_cost_workspace_floats": [c_i, c_i, c_i, c_i],
     "uenc_match_cost": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p],
     "uenc_lsap_solve": [c_p, c_i, c_i, c_p],
+    # set criterion: point-sampled mask / dice losses and the class loss (csrc/criterion.hip)
+    "uenc_crit_point_logits": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    "uenc_crit_mask_loss_fwd": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "uenc_crit_mask_loss_bwd": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p],
+    "uenc_crit_class_loss": [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_p],
     # view synthesis + photometric loss of MonodepthLoss (csrc/monodepth.hip)
     "uenc_view_synth_workspace_floats": [c_i, c_i, c_i, c_i, c_i],
     "uenc_view_synth_fwd": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],

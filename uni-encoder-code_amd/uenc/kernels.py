@@ -1093,6 +1093,118 @@ def lsap_solve(cost: torch.Tensor, Ts):
     return out[0], out[1], offs
 
 
+# ---- set criterion (csrc/criterion.hip) ---------------------------------------------------------------------------------------------------
+CRIT_MAX_HEADS, CRIT_MAX_IMAGES = 16, 32        # of csrc/criterion.hip: heads and images of one call
+
+
+class CritCall:
+    """The shapes and the 1024-byte descriptor (struct CritDesc) the four uenc_crit_* entry points of one criterion call share.
+    masks: per head (bs, Q, h, w) f32 or None; logits: per head (bs, Q, C1) f32 or None; gts: per image (T, Hg, Wg) uint8; labels: per image
+    (T) int64.  Row r = head * N + n of every buffer is pair n of that head, N = sum_b min(Q, T_b)."""
+
+    def __init__(self, masks, logits, gts, labels):
+        import numpy as np
+        first = masks[0] if masks[0] is not None else logits[0]
+        self.n_heads, self.bs, self.Q = len(masks), int(first.shape[0]), int(first.shape[1])
+        if not (1 <= self.n_heads <= CRIT_MAX_HEADS and 1 <= self.bs <= CRIT_MAX_IMAGES and len(logits) == self.n_heads and len(gts) == len(labels) == self.bs):
+            raise capi.UencError(f"criterion: at most {CRIT_MAX_HEADS} heads and {CRIT_MAX_IMAGES} images per call, one target entry per image")
+        self.h = self.w = self.C1 = 0
+        for mk, lg in zip(masks, logits):
+            if mk is not None:
+                _dev(mk, "pred_masks", torch.float32, 4)
+                self.h, self.w = int(mk.shape[2]), int(mk.shape[3])
+                if tuple(mk.shape) != (self.bs, self.Q, self.h, self.w) or tuple(mk.shape) != tuple(masks[0].shape):
+                    raise capi.UencError("criterion: every head's pred_masks must have one shape")
+            if lg is not None:
+                _dev(lg, "pred_logits", torch.float32, 3)
+                self.C1 = int(lg.shape[2])
+                if tuple(lg.shape) != (self.bs, self.Q, self.C1) or tuple(lg.shape) != tuple(logits[0].shape):
+                    raise capi.UencError("criterion: every head's pred_logits must have one shape")
+        self.Ts = [int(g.shape[0]) for g in gts]
+        self.Hg = self.Wg = 1
+        desc = np.zeros(1, dtype=np.dtype([("head", [("masks", "<u8"), ("logits", "<u8")], CRIT_MAX_HEADS),
+                                           ("img", [("gt", "<u8"), ("labels", "<u8"), ("T", "<i4"), ("pair0", "<i4")], CRIT_MAX_IMAGES)]))
+        assert desc.itemsize == 1024
+        for i, (mk, lg) in enumerate(zip(masks, logits)):
+            desc["head"][0, i] = (ptr(mk), ptr(lg))
+        pairs = 0
+        for b, (gt, lab) in enumerate(zip(gts, labels)):
+            T = self.Ts[b]
+            if T:
+                _dev(gt, "target masks", torch.uint8, 3); _dev(lab, "labels", torch.int64, 1)
+                if pairs == 0:                          # the first image with targets sets the size
+                    self.Hg, self.Wg = int(gt.shape[1]), int(gt.shape[2])
+                if tuple(gt.shape[1:]) != (self.Hg, self.Wg) or lab.shape[0] != T:
+                    raise capi.UencError("criterion: target masks must share one (padded) size and come with one label each")
+            desc["img"][0, b] = (gt.data_ptr() if T else 0, lab.data_ptr() if T else 0, T, pairs)
+            pairs += min(self.Q, T)
+        self.N, self.desc, self.device = pairs, desc, first.device
+        self._keep = (masks, logits, gts, labels)       # the descriptor holds raw pointers
+
+    def _rows(self, t, name, dtype, tail):
+        _dev(t, name, dtype, 1 + len(tail))
+        if tuple(t.shape) != (self.n_heads * self.N,) + tuple(tail):
+            raise capi.UencError(f"criterion: {name} must be {(self.n_heads * self.N,) + tuple(tail)}, got {tuple(t.shape)}")
+        return t
+
+
+def crit_point_logits(call: CritCall, row_ind, points):
+    """points (heads * N, M, 2) -> (heads * N, M): every pair's predicted logit map at its M points (uenc_crit_point_logits)."""
+    M = int(points.shape[1])
+    call._rows(row_ind, "row_ind", torch.int64, ()); call._rows(points, "points", torch.float32, (M, 2))
+    out = torch.empty((call.n_heads * call.N, M), dtype=torch.float32, device=call.device)
+    check(lib.uenc_crit_point_logits(call.desc.ctypes.data, call.n_heads, call.bs, call.Q, call.h, call.w, call.N, M, row_ind.data_ptr(),
+                                     points.data_ptr(), out.data_ptr(), stream_ptr()), "crit_point_logits")
+    return out
+
+
+def crit_mask_loss_fwd(call: CritCall, row_ind, col_ind, points, need_grad: bool = True):
+    """points (heads * N, P, 2) -> loss (heads * N, 2) = ce_n, dice_n; sums (heads * N, 3) = sum s t, sum s, sum t; and, for the backward,
+    unit (heads * N, P, 2) and keys (heads * N, 4 P) int32 (None, None without need_grad).  uenc_crit_mask_loss_fwd."""
+    P, R = int(points.shape[1]), call.n_heads * call.N
+    call._rows(row_ind, "row_ind", torch.int64, ()); call._rows(col_ind, "col_ind", torch.int64, ()); call._rows(points, "points", torch.float32, (P, 2))
+    loss = torch.empty((R, 2), dtype=torch.float32, device=call.device)
+    sums = torch.empty((R, 3), dtype=torch.float32, device=call.device)
+    unit = torch.empty((R, P, 2), dtype=torch.float32, device=call.device) if need_grad else None
+    keys = torch.empty((R, 4 * P), dtype=torch.int32, device=call.device) if need_grad else None
+    check(lib.uenc_crit_mask_loss_fwd(call.desc.ctypes.data, call.n_heads, call.bs, call.Q, call.h, call.w, call.Hg, call.Wg, call.N, P,
+                                      row_ind.data_ptr(), col_ind.data_ptr(), points.data_ptr(), loss.data_ptr(), sums.data_ptr(), ptr(unit),
+                                      ptr(keys), stream_ptr()), "crit_mask_loss_fwd")
+    return loss, sums, unit, keys
+
+
+def crit_mask_loss_bwd(call: CritCall, row_ind, points, unit, sorted_keys, order, gce, gdice, inv_num_masks: float):
+    """-> (heads, bs, Q, h, w): the gradient of every head's mask logits from the per-head upstream gradients gce / gdice (heads) of the summed
+    ce_n / dice_n times inv_num_masks.  sorted_keys / order: the stable sort of the forward's keys along dim 1.  uenc_crit_mask_loss_bwd."""
+    P = int(points.shape[1])
+    call._rows(row_ind, "row_ind", torch.int64, ()); call._rows(points, "points", torch.float32, (P, 2)); call._rows(unit, "unit", torch.float32, (P, 2))
+    call._rows(sorted_keys, "sorted_keys", torch.int32, (4 * P,)); call._rows(order, "order", torch.int64, (4 * P,))
+    for g in (gce, gdice):
+        _dev(g, "upstream gradient", torch.float32, 1)
+        if g.shape[0] != call.n_heads:
+            raise capi.UencError("criterion: one upstream gradient per head")
+    gmasks = torch.zeros((call.n_heads, call.bs, call.Q, call.h, call.w), dtype=torch.float32, device=call.device)
+    check(lib.uenc_crit_mask_loss_bwd(call.desc.ctypes.data, call.n_heads, call.bs, call.Q, call.h, call.w, call.N, P, row_ind.data_ptr(),
+                                      points.data_ptr(), unit.data_ptr(), sorted_keys.data_ptr(), order.data_ptr(), gce.data_ptr(), gdice.data_ptr(),
+                                      inv_num_masks, gmasks.data_ptr(), stream_ptr()), "crit_mask_loss_bwd")
+    return gmasks
+
+
+def crit_class_loss(call: CritCall, row_ind, col_ind, eos_coef: float):
+    """-> loss (heads), grad (heads, bs * Q, C1): F.cross_entropy(logits, target classes built from the indices, weights (1, ..., 1, eos_coef))
+    of every head and its gradient.  row_ind / col_ind may be None when there is no pair.  uenc_crit_class_loss."""
+    if call.N:
+        call._rows(row_ind, "row_ind", torch.int64, ()); call._rows(col_ind, "col_ind", torch.int64, ())
+    R = call.bs * call.Q
+    rows = torch.empty((call.n_heads, R, 2), dtype=torch.float32, device=call.device)
+    loss = torch.empty(call.n_heads, dtype=torch.float32, device=call.device)
+    grad = torch.empty((call.n_heads, R, call.C1), dtype=torch.float32, device=call.device)
+    check(lib.uenc_crit_class_loss(call.desc.ctypes.data, call.n_heads, call.bs, call.Q, call.C1, call.N, ptr(row_ind) if call.N else 0,
+                                   ptr(col_ind) if call.N else 0, eos_coef, rows.data_ptr(), loss.data_ptr(), grad.data_ptr(), stream_ptr()),
+          "crit_class_loss")
+    return loss, grad
+
+
 # ---- MonodepthLoss: view synthesis + photometric loss (csrc/monodepth.hip) -----------------------------------------------------------------
 # slots of the 67-pointer descriptor of uenc_view_synth_fwd / _bwd (struct VsDesc)
 _VS = {"disp": 0, "cflow": 4, "mask": 12, "T": 20, "K": 21, "invK": 22, "src": 23, "color": 24, "sample": 25, "sample_ego": 26, "sample_cmp": 27,

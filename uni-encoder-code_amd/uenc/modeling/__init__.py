@@ -9,5 +9,7 @@ from .transformer_decoder.oneformer_transformer_decoder import ContrastiveMultiS
 from .meta_arch.oneformer_head import OneFormerHead
 from . import matcher
 from .matcher import HungarianMatcher
+from . import criterion
+from .criterion import SetCriterion, build_criterion
 from . import monodepth_loss
 from .monodepth_loss import MonodepthLoss

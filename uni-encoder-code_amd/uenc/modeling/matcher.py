@@ -16,7 +16,7 @@ One deviation, device solver only: the reference returns an EMPTY assignment whe
 the device cannot make a result's shape depend on values, so there an all-NaN matrix is treated like any NaN (entries 100).
 
 CPU inputs run the same formulas in plain torch + scipy.  Target masks are 0 / 1 (bool, uint8 or float), already padded to one size per
-call.  The loss that uses the indices (the set criterion) is the caller's: the reference ships none.
+call.  The loss that uses the indices is uenc.modeling.criterion.SetCriterion (the reference ships none).
 """
 from typing import List, Optional, Sequence, Tuple
 
