@@ -389,7 +389,8 @@ int uenc_postproc_panoptic_label(const float* mask_logits, const int* ids, const
  *   gemm_tn_f32:  dW (N, K) += dY^T X, db (N) += column sums of dY (db may be NULL); dY (M, N), X (M, K) fp32, N, K % 4 == 0
  *   window_attn_f32_{fwd,bwd}: qkv (B, H, W, 3C) fp32, qkv_bias (3C), table ((2ws-1)^2, nH) = relative_position_bias_table,
  *                 out / dout (B, H, W, C); same pad / shift / mask semantics as uenc_window_attn_* (model/modeling/backbone/
- *                 swin.py:250-289, :131-171, :414-440).  bwd: dqkv written, dtable and dbias_pad (3C) accumulated (atomics)
+ *                 swin.py:250-289, :131-171, :414-440) and the same window domain: ws 1 .. 12, 0 <= shift < ws, C == 32 nH; anything
+ *                 else is UENC_EINVAL before a launch.  bwd: dqkv written, dtable and dbias_pad (3C) accumulated (atomics)
  *   mha_f32_{fwd,bwd}: the decoder's nn.MultiheadAttention cores, tensor contract of uenc_mha_* with fp32 tensors; lse (B, nH, Lq);
  *                 bwd: dq written, dk / dv (zeroed by the caller) accumulated, delta (B, nH, Lq) scratch
  *   na2d_f32_{fwd,bwd}: DiNAT's neighbourhood attention, tensor contract and limits of uenc_na2d_* with fp32 tensors: qkv

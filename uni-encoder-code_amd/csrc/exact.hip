@@ -340,7 +340,8 @@ __global__ void xwin_bwd_kernel(XWin p) {
 }
 
 static int xwin_fill(XWin& p, int B, int H, int W, int C, int nH, int ws, int shift, float scale) {
-    UENC_CHECK_ARG(B > 0 && H > 0 && W > 0 && C == nH * XHD && ws >= 2 && ws <= 16 && shift >= 0 && shift < ws);
+    // the window domain of uenc_window_attn_*: 1 .. 12 (beyond it the forward's three staged images would not fit 64 KB of LDS)
+    UENC_CHECK_ARG(B > 0 && H > 0 && W > 0 && nH > 0 && C == nH * XHD && ws >= 1 && ws <= 12 && shift >= 0 && shift < ws);
     p.B = B; p.H = H; p.W = W; p.C = C; p.nH = nH; p.ws = ws; p.shift = shift; p.scale = scale;
     p.Hp = (H + ws - 1) / ws * ws; p.Wp = (W + ws - 1) / ws * ws;
     p.nWw = p.Wp / ws; p.nWin = (p.Hp / ws) * p.nWw; p.N = ws * ws;

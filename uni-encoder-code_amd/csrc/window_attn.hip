@@ -955,9 +955,10 @@ extern "C" long uenc_window_attn_bwd_ws_floats(int B, int H, int W, int nH, int 
     return (long)nH * G * np * np;
 }
 
-// dgrads: (nH * (2ws-1)^2 + 3C) fp32, overwritten: the gradient of the relative-position table as [head][(2ws-1)^2], then
-// the q | k | v (3C) slice of the qkv-bias gradient that flows through padding slots.  dS_ws: scratch of
-// uenc_window_attn_bwd_ws_floats() floats.
+// dqkv (B, H, W, 3C) bf16 is written.  The two parameter gradients are ACCUMULATED (float atomics) into the caller's buffers: dtable
+// ((2ws-1)^2, nH) fp32, the relative-position table's gradient in the parameter's own layout, and dbias_pad (3C) fp32, the q | k | v
+// slice of the qkv-bias gradient that flows through padding slots.  dS_ws: scratch of uenc_window_attn_bwd_ws_floats() floats
+// (overwritten; defer_dtable != 0 leaves the dense dS partials there for uenc_window_attn_dtable_grouped and adds nothing to dtable).
 extern "C" int uenc_window_attn_bwd(const void* qkv, const void* qkv_bias, const float* bias_q, const float* bias_k,
                                     const void* o_saved, const float* lse, const void* d_out, void* dqkv, float* dS_ws, float* dtable, float* dbias_pad,
                                     int B, int H, int W, int C, int nH, int ws, int shift, float scale, int defer_dtable, hipStream_t stream) {
