@@ -202,6 +202,20 @@ def test_small_reductions_arena_and_descriptors():
     q.clear()
     assert not q and q.alloc(10, dev).data_ptr() == a.data_ptr() and len(q._chunks) == 2              # the arena is reused, not re-allocated
     assert np.dtype(K.SmallReductions._LN).itemsize == 40 and np.dtype(K.SmallReductions._DT).itemsize == 40
+    # release() gives the chunks back; a buffer handed out before stays readable and writable (it is a view into its chunk), a parked one
+    # stays in `keep`, and the next alloc starts a fresh chunk at offset 0
+    old = q.alloc(500, dev)
+    old.fill_(3.0)
+    q.add_ln(old, torch.zeros(8), torch.zeros(8), 4, 8)
+    q.release()
+    assert q._chunks == [] and len(q.keep) == 1 and q.keep[0][0] is old
+    new = q.alloc(500, dev)
+    assert len(q._chunks) == 1 and new.data_ptr() == q._chunks[0].data_ptr() and q._chunks[0].numel() == q.CHUNK
+    new.fill_(5.0)
+    assert float(old.sum()) == 1500.0                                                                 # disjoint from the fresh chunk
+    old.add_(1.0)
+    assert float(old.sum()) == 2000.0 and float(new.sum()) == 2500.0
+    assert q.alloc(10, dev).data_ptr() == new.data_ptr() + 2048                                       # the bump pointer was rewound with it
     # the library's own rule for when a LayerNorm backward stores block partials (few rows: it adds its sums itself, nothing to defer)
     assert K.lib.uenc_layernorm_bwd_blocks(16384, 768) == 2048 and K.lib.uenc_layernorm_bwd_blocks(300, 256) == 0
     assert K.lib.uenc_window_attn_bwd_groups(2, 64, 128, 24, 12) == 10

@@ -368,7 +368,7 @@ def test_forward_after_step_sees_the_new_weights(U):
     ops.begin_step(fresh_grads=True)
     casts = ops.CACHE.casts
     forward()
-    planned = [k for k, e in ops.CACHE._store.items() if e[4] is not None]
+    planned = [k for k, e in ops.CACHE._store.items() if e.plan is not None]
     assert planned and ops.CACHE.casts - casts <= len(ops.CACHE._store) - len(planned)
 
 

@@ -2,7 +2,7 @@
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uni-encoder-code_amd"))
 from uenc import ops
-from uenc.ops import WgradQueue
+from uenc.ops import WgradQueue, WgradWork
 
 def build(M, C, layers):
     probs = []
@@ -17,12 +17,8 @@ def build(M, C, layers):
 def descs(probs, tile, tokens):
     out, fl = [], 0.0
     for dy, x, gw, gb in probs:
-        M, N, Kd = dy.shape[0], dy.shape[1], x.shape[1]
-        nsplit = max(1, -(-M // tokens)); mlen = -(-(M // 64) // nsplit) * 64; nsplit = -(-M // mlen)
-        tiles_k = -(-Kd // tile)
-        items = -(-N // tile) * tiles_k * nsplit
-        out.append((dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb.data_ptr(), dy.stride(0), x.stride(0), gw.stride(0), M, N, Kd, tiles_k, mlen, nsplit, items, 0))
-        fl += 2.0 * M * N * Kd
+        out.append(WgradWork.of(dy, x, gw, gb, tile, max(1, -(-dy.shape[0] // tokens))))
+        fl += 2.0 * dy.shape[0] * dy.shape[1] * x.shape[1]
     return out, fl
 
 def timeit(fn, n=5):
@@ -39,5 +35,5 @@ for tag, M, C in [("s1", 262144, 192), ("s2", 65536, 384), ("s3x6", 16384, 768),
     for tile, tokens in [(128, 4096), (256, 8192), (256, 16384)]:
         d, fl = descs(probs, tile, tokens)
         t = timeit(lambda: WgradQueue.launch(tile, d, probs[0][0].device))
-        print(f"{tag} tile {tile} tokens/item {tokens:6d}: {sum(x[13] for x in d):5d} items  {t*1e3:8.1f} us {fl/t/1e9:6.0f} TF/s", flush=True)
+        print(f"{tag} tile {tile} tokens/item {tokens:6d}: {sum(w.items for w in d):5d} items  {t*1e3:8.1f} us {fl/t/1e9:6.0f} TF/s", flush=True)
     del probs

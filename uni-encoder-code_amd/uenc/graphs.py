@@ -104,7 +104,9 @@ class GraphedTrainStep:
             K.CAPTURE_ARENA = None
         # the graph reads (and, at its start, rewrites) the bf16 operand copies that existed at capture time: they stay allocated even
         # when the cache replaces an entry (a forward between replays after the weights moved)
-        self._operands = [e[2] for e in ops.CACHE._store.values()]
+        self._operands = [e.operand for e in ops.CACHE._store.values()]
+        # likewise the arena chunks its parked partial sums are written to, which CACHE.invalidate() (a checkpoint load) gives back
+        self._partials = list(ops.SMALLQ._chunks)
         torch.cuda.synchronize(self.device)
 
     def _run(self):

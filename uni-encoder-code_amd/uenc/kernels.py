@@ -4,10 +4,14 @@ Every wrapper validates what the kernel's grid assumes (device, dtype, inner str
 handing raw pointers to the library; the library re-checks alignment and sizes and refuses
 (-1) rather than launching on a bad shape.
 """
+import collections
 import ctypes
+import itertools
+import operator
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import capi
@@ -49,7 +53,6 @@ CAPTURE_ARENA = None
 def upload_table(arr, device, pinned: bool = True) -> torch.Tensor:
     """Device copy of a numpy descriptor table (raw bytes).  Eager: a pinned (or, pinned=False, pageable) temporary and torch's copy, as the
     launch sites always did; during a capture: staged in the capture's host arena."""
-    import numpy as np
     raw = arr.view(np.uint8).reshape(-1)
     if CAPTURE_ARENA is None:
         if not pinned:
@@ -65,6 +68,18 @@ def upload_table(arr, device, pinned: bool = True) -> torch.Tensor:
     tab = torch.empty(n, dtype=torch.uint8, device=device)
     check(lib.uenc_upload(tab.data_ptr(), host.data_ptr() + off, n, stream_ptr()), "upload")
     return tab
+
+
+def pack_table(dtype, recs, counts, begin: str):
+    """Descriptor table of a grouped launch: every field of `dtype` read from the records' attribute of the same name, except `pad`
+    (zero) and `begin`, the running sum of `counts` (the work items / workgroups of each record).  -> (numpy table, the count in all)"""
+    names = [f for f, _ in dtype if f not in (begin, "pad")]
+    tab = np.zeros(len(recs), dtype=dtype)
+    tab[names] = list(map(operator.attrgetter(*names), recs))
+    begins = [0, *itertools.accumulate(counts)]
+    total = begins.pop()
+    tab[begin] = begins
+    return tab, total
 
 
 class SeedSlot:
@@ -150,7 +165,6 @@ def step_rng_advance(state: torch.Tensor, keep_prob: torch.Tensor, n_branch: int
 
 def _mix32_np(seed, idx):
     """uenc_mix32 of common.h on numpy uint64 arrays (seed: uint32 values, idx: uint64) -> uint32 values as uint64."""
-    import numpy as np
     M = np.uint64(0xFFFFFFFF)
     idx = np.asarray(idx, dtype=np.uint64)
     x = (((idx & M) ^ (((idx >> np.uint64(32)) * np.uint64(0x9E3779B9)) & M)) + np.asarray(seed, dtype=np.uint64)) & M
@@ -163,7 +177,6 @@ def _mix32_np(seed, idx):
 def step_rng_reference(base_seed: int, step: int, keep_prob, n_samples: int, n_seed: int):
     """The tables uenc_step_rng_advance writes for (base seed, step), restated on the host with numpy integer / fp32 arithmetic.
     -> (scales (len(keep_prob), n_samples) float32, seeds (n_seed,) uint32).  `step` is the counter value AFTER the advance."""
-    import numpy as np
     base, step = np.uint64(int(base_seed) & (2 ** 64 - 1)), np.uint64(int(step) & (2 ** 64 - 1))
     h = _mix32_np(base >> np.uint64(32), step)
     key = _mix32_np((base & np.uint64(0xFFFFFFFF)) ^ h, step)
@@ -566,6 +579,8 @@ class SmallReductions:
     queue is flushed (ops.WgradQueue.flush: with the deferred weight-gradient groups, and at the end of every backward pass)."""
     _LN = [("part", "<u8"), ("dgamma", "<u8"), ("dbeta", "<u8"), ("nblk", "<i4"), ("C", "<i4"), ("begin", "<i4"), ("pad", "<i4")]
     _DT = [("wsd", "<u8"), ("dtab", "<u8"), ("G", "<i4"), ("nH", "<i4"), ("ws", "<i4"), ("ntiles", "<i4"), ("begin", "<i4"), ("pad", "<i4")]
+    LnSum = collections.namedtuple("LnSum", "part dgamma dbeta nblk C")                  # the records' fields, by the structs' names
+    TableSum = collections.namedtuple("TableSum", "wsd dtab G nH ws ntiles")
 
     CHUNK = 64 << 20          # floats' worth of bytes per arena chunk
 
@@ -593,36 +608,31 @@ class SmallReductions:
         return bool(self.ln or self.dt)
 
     def add_ln(self, part, dgamma, dbeta, nblk: int, C: int):
-        self.ln.append((part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), nblk, C))
+        self.ln.append(self.LnSum(part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), nblk, C))
         self.keep.append((part, dgamma, dbeta))
 
     def add_dtable(self, wsd, dtab, G: int, nH: int, ws: int, ntiles: int):
-        self.dt.append((wsd.data_ptr(), dtab.data_ptr(), G, nH, ws, ntiles))
+        self.dt.append(self.TableSum(wsd.data_ptr(), dtab.data_ptr(), G, nH, ws, ntiles))
         self.keep.append((wsd, dtab))
 
     def clear(self):
         self.ln, self.dt, self.keep = [], [], []
         self._cur, self._off = 0, 0           # stream order: whatever is parked next is written after the reductions launched above
 
+    def release(self):
+        """Give the arena back to the allocator (a model that goes on to inference only has no use for it).  Buffers parked and not
+        yet flushed stay valid: `keep` holds views into their chunks.  The next alloc() starts a fresh chunk."""
+        self._chunks, self._cur, self._off = [], 0, 0
+
     def flush(self):
-        import numpy as np
         dev = self.keep[0][0].device if self.keep else None
         if self.ln:
-            desc = np.zeros(len(self.ln), dtype=self._LN)
-            begin = 0
-            for i, (part, dg, db, nblk, C) in enumerate(self.ln):
-                desc[i] = (part, dg, db, nblk, C, begin, 0)
-                begin += -(-2 * C // 64)
-            tab = upload_table(desc, dev)
-            check(lib.uenc_ln_param_grouped(tab.data_ptr(), len(self.ln), begin, stream_ptr()), "ln_param_grouped")
+            tab, blocks = pack_table(self._LN, self.ln, [-(-2 * r.C // 64) for r in self.ln], "begin")
+            check(lib.uenc_ln_param_grouped(upload_table(tab, dev).data_ptr(), len(self.ln), blocks, stream_ptr()), "ln_param_grouped")
         if self.dt:
-            desc = np.zeros(len(self.dt), dtype=self._DT)
-            begin = 0
-            for i, (wsd, dtab, G, nH, ws, nt) in enumerate(self.dt):
-                desc[i] = (wsd, dtab, G, nH, ws, nt, begin, 0)
-                begin += nH * nt
-            tab = upload_table(desc, dev)
-            check(lib.uenc_window_attn_dtable_grouped(tab.data_ptr(), len(self.dt), begin, stream_ptr()), "window_attn_dtable_grouped")
+            tab, blocks = pack_table(self._DT, self.dt, [r.nH * r.ntiles for r in self.dt], "begin")
+            check(lib.uenc_window_attn_dtable_grouped(upload_table(tab, dev).data_ptr(), len(self.dt), blocks, stream_ptr()),
+                  "window_attn_dtable_grouped")
         self.clear()
 
 
@@ -1012,7 +1022,6 @@ LSAP_MAX = 256                  # LSAP_MAX_N of csrc/matcher.hip: most queries /
 
 
 def _match_dtypes():
-    import numpy as np
     mp = np.dtype([("logits", "<u8"), ("masks", "<u8"), ("points", "<u8"), ("gt", "<u8"), ("labels", "<u8"), ("T", "<i4"), ("pad", "<i4")])
     lp = np.dtype([("cost", "<u8"), ("row_ind", "<u8"), ("col_ind", "<u8"), ("T", "<i4"), ("ld", "<i4")])
     assert mp.itemsize == 48 and lp.itemsize == 32
@@ -1031,7 +1040,6 @@ def match_cost(problems, w_class: float, w_mask: float, w_dice: float, nan_fill:
     """problems = [(logits (Q, C1) f32, masks (Q, h, w) f32, points (P, 2) f32, gt (T, Hg, Wg) uint8, labels (T) int64), ...], all on one
     GPU, same Q / C1 / h / w / P / Hg / Wg, any T per problem -> cost (n_prob, Q, Tmax) fp32 with Tmax = max(1, max T); columns >= a
     problem's T are zero.  One call of uenc_match_cost; the descriptors travel in the kernel arguments."""
-    import numpy as np
     mp, _ = _match_dtypes()
     n = len(problems)
     if n == 0:
@@ -1072,7 +1080,6 @@ def lsap_solve(cost: torch.Tensor, Ts):
     """cost (n_prob, Q, ld) fp32 on the GPU, problem p being cost[p, :, :Ts[p]] -> (row_ind, col_ind, offsets): two flat int64 device buffers
     holding min(Q, Ts[p]) pairs per problem from offsets[p] on (scipy's convention: row_ind ascending).  One call of uenc_lsap_solve, no
     synchronisation; the offsets are host integers because the shapes are."""
-    import numpy as np
     _, lp = _match_dtypes()
     _dev(cost, "cost", torch.float32, 3)
     n, Q, ld = cost.shape
@@ -1103,7 +1110,6 @@ class CritCall:
     (T) int64.  Row r = head * N + n of every buffer is pair n of that head, N = sum_b min(Q, T_b)."""
 
     def __init__(self, masks, logits, gts, labels):
-        import numpy as np
         first = masks[0] if masks[0] is not None else logits[0]
         self.n_heads, self.bs, self.Q = len(masks), int(first.shape[0]), int(first.shape[1])
         if not (1 <= self.n_heads <= CRIT_MAX_HEADS and 1 <= self.bs <= CRIT_MAX_IMAGES and len(logits) == self.n_heads and len(gts) == len(labels) == self.bs):
@@ -1214,7 +1220,6 @@ _VS_SLOTS = 67
 
 def _vs_desc(mode, K, inv_K, src, T, disps, cflows, masks):
     """Checks the inputs of one view-synthesis call and fills the input slots -> (descriptor, S, NF, B, H, W)."""
-    import numpy as np
     _dev(src, "src", torch.float32, 5)
     NF, B, _, H, W = src.shape
     S = len(disps)

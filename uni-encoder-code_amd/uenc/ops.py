@@ -10,14 +10,17 @@ Conventions
     data-parallel wrapper (`uenc.dp`) can point `.grad` at flat all-reduce buckets beforehand.
 """
 import copy
+import dataclasses
 import os
 import weakref
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import kernels as K
+from .capi import check, lib, stream_ptr
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -25,77 +28,95 @@ BF16, F32 = torch.bfloat16, torch.float32
 # --------------------------------------------------------------------------------------------
 # parameter operand cache and gradient buffers
 # --------------------------------------------------------------------------------------------
+class CastPiece(NamedTuple):
+    """One rectangle of the batched refresh: fp32 rows x cols at byte `src_off` of owner number `owner`, cast to bf16 at element `dst_off` of
+    the operand.  tr: 0 plain, 1 transposed, | ld << 4 when the destination's row stride is not the piece's own width."""
+    owner: int; src_off: int; dst_off: int
+    rows: int; cols: int; tr: int
+
+
+class RelposPlan(NamedTuple):                     # the operand is the expanded relative-position bias of a (2 ws - 1)^2 x nH table
+    ws: int; nH: int
+
+
+@dataclasses.dataclass(slots=True)
+class CacheEntry:
+    sig: Tuple[Tuple[int, int], ...]              # (version, data_ptr) of every owner when the operand was last made or refreshed
+    owners: Tuple[weakref.ref, ...]               # one or two master parameters
+    operand: torch.Tensor
+    plan: Union[List[CastPiece], RelposPlan, None]    # how refresh() re-makes the operand in place; None: dropped there, re-made lazily
+
+    def moved(self) -> bool:                      # an owner died or its storage moved
+        for ref, (_, ptr) in zip(self.owners, self.sig):
+            p = ref()
+            if p is None or p.data_ptr() != ptr:
+                return True
+        return False
+
+
+class RefreshTables(NamedTuple):
+    """Device descriptor tables of the two grouped refresh launches, kept while the set of entries is unchanged."""
+    cast: Optional[torch.Tensor]; ncast: int; tiles: int
+    relpos: Optional[torch.Tensor]; nrelpos: int; blocks: int
+
+
 class ParamCache:
     """bf16 (optionally transposed / zero-padded) copies of fp32 parameters, keyed by version.
 
     `refresh()` re-casts every cached copy in place with ONE batched kernel launch (instead of one tiny launch per
     tensor): call it after each optimizer step; entries are otherwise re-made lazily when a parameter's version or
     storage changed."""
+    _CAST = [("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("tr", "<i4"), ("tc", "<i4"), ("tb", "<i8")]
+    _RELPOS = [("table", "<u8"), ("bias_q", "<u8"), ("bias_k", "<u8"), ("nH", "<i4"), ("ws", "<i4"), ("NP", "<i4"), ("blk_begin", "<i4")]
 
     def __init__(self):
         self._store = {}
         self.casts = 0
-        self._table = None          # (device descriptor tensor, n, total_tiles, keys)
+        self._table: Optional[RefreshTables] = None
 
     def invalidate(self):
         self._store.clear()
         self._table = None
+        SMALLQ.release()
 
-    def _get(self, p: torch.Tensor, kind, make, plan=None):
-        key = (id(p), kind)
+    def _get(self, owners: Tuple[torch.Tensor, ...], kind, make):
+        """The operand that `make() -> (operand, plan)` derives from one or two parameters, valid while every owner is alive, the same
+        object, and at the same version and data_ptr."""
+        key = (kind, *[id(p) for p in owners])
         ent = self._store.get(key)
-        # id() of a dead tensor can be reused by a new one (with the same storage address and version 0):
-        # the weak reference tells a live owner from a recycled id
-        if ent is not None and ent[3]() is p and ent[0] == p._version and ent[1] == p.data_ptr():
-            return ent[2]
-        t = make()
+        if ent is not None:                         # (an explicit loop: some six hundred lookups per step)
+            for ref, (version, ptr), p in zip(ent.owners, ent.sig, owners):
+                # id() of a dead tensor can be reused by a new one (with the same storage address and version 0):
+                # the weak reference tells a live owner from a recycled id
+                if ref() is not p or p._version != version or p.data_ptr() != ptr:
+                    break
+            else:
+                return ent.operand
+        t, plan = make()
         self.casts += 1
-        self._store[key] = (p._version, p.data_ptr(), t, weakref.ref(p), plan)
+        self._store[key] = CacheEntry(tuple([(p._version, p.data_ptr()) for p in owners]), tuple([weakref.ref(p) for p in owners]), t, plan)
         self._table = None
         return t
 
-    @staticmethod
-    def _mat_view(p, rows):
+    def _mat(self, p, rows, transposed):
         w = p.detach().reshape(p.shape[0], -1)
-        return w if rows is None else w[rows[0]:rows[1]]
+        w = w if rows is None else w[rows[0]:rows[1]]
+        N, Kd = w.shape
+        aligned = N % 8 == 0 and Kd % 8 == 0
+
+        def make():
+            ww = w if aligned else torch.nn.functional.pad(w, (0, -Kd % 8, 0, -N % 8))
+            plan = [CastPiece(0, (rows[0] if rows else 0) * Kd * 4, 0, N, Kd, int(transposed))] if (aligned and not K.EXACT) else None
+            return K.cast_transpose_bf16(ww.contiguous()) if transposed else K.cast_bf16(ww.contiguous()), plan
+        return self._get((p,), ("t" if transposed else "m", rows), make)
 
     def mat(self, p: torch.Tensor, rows: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """(N, K) bf16 view of a Linear / 1x1-conv weight, rows [a, b) if given; K, N padded to 8."""
-        w = self._mat_view(p, rows)
-        N, Kd = w.shape
-        aligned = N % 8 == 0 and Kd % 8 == 0
-
-        def make():
-            ww = w if aligned else torch.nn.functional.pad(w, (0, -Kd % 8, 0, -N % 8))
-            return K.cast_bf16(ww.contiguous())
-        plan = ((rows[0] if rows else 0) * Kd * 4, N, Kd, 0) if (aligned and not K.EXACT) else None
-        return self._get(p, ("m", rows), make, plan)
+        return self._mat(p, rows, False)
 
     def mat_t(self, p: torch.Tensor, rows: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """(K, N) bf16: the transposed operand the dgrad GEMM reads."""
-        w = self._mat_view(p, rows)
-        N, Kd = w.shape
-        aligned = N % 8 == 0 and Kd % 8 == 0
-
-        def make():
-            ww = w if aligned else torch.nn.functional.pad(w, (0, -Kd % 8, 0, -N % 8))
-            return K.cast_transpose_bf16(ww.contiguous())
-        plan = ((rows[0] if rows else 0) * Kd * 4, N, Kd, 1) if (aligned and not K.EXACT) else None
-        return self._get(p, ("t", rows), make, plan)
-
-    def _get2(self, p1, p2, kind, make, plan=None):
-        """Like _get for an operand derived from two parameters (valid while neither changed).  plan: a LIST of
-        (source byte pointer, destination element offset, rows, cols, transpose | ld << 4) pieces for the batched refresh."""
-        key = (id(p1), (kind, id(p2)))
-        ent = self._store.get(key)
-        sig = (p1._version, p1.data_ptr(), p2._version, p2.data_ptr())
-        if ent is not None and ent[3]() is p1 and ent[5]() is p2 and ent[0] == sig:
-            return ent[2]
-        t = make()
-        self.casts += 1
-        self._store[key] = (sig, p1.data_ptr(), t, weakref.ref(p1), plan, weakref.ref(p2))
-        self._table = None
-        return t
+        return self._mat(p, rows, True)
 
     def cat(self, p1: torch.Tensor, p2: torch.Tensor, transposed: bool = False) -> torch.Tensor:
         """bf16 [p1; p2] stacked along the output dimension ((N1+N2, K), or its (K, N1+N2) transpose): two Linear layers that
@@ -106,31 +127,30 @@ class ParamCache:
 
         def make():
             w = torch.cat([p1.detach().reshape(N1, -1), p2.detach().reshape(N2, -1)], 0).contiguous()
-            return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
-        plan = None
-        if (not K.EXACT and p1.is_contiguous() and p2.is_contiguous() and p2.numel() // N2 == Kd and Kd % 8 == 0 and N1 % 8 == 0 and N2 % 8 == 0
-                and p1.dtype == F32 and p2.dtype == F32):
-            ld = N1 + N2
-            plan = ([(p1.data_ptr(), 0, N1, Kd, 1 | (ld << 4)), (p2.data_ptr(), N1, N2, Kd, 1 | (ld << 4))] if transposed
-                    else [(p1.data_ptr(), 0, N1, Kd, 0), (p2.data_ptr(), N1 * Kd, N2, Kd, 0)])
-        return self._get2(p1, p2, "catT" if transposed else "cat", make, plan)
+            plan = None
+            if (not K.EXACT and p1.is_contiguous() and p2.is_contiguous() and p2.numel() // N2 == Kd and Kd % 8 == 0 and N1 % 8 == 0
+                    and N2 % 8 == 0 and p1.dtype == F32 and p2.dtype == F32):
+                tr = 1 | ((N1 + N2) << 4) if transposed else 0
+                plan = [CastPiece(0, 0, 0, N1, Kd, tr), CastPiece(1, 0, N1 if transposed else N1 * Kd, N2, Kd, tr)]
+            return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w), plan
+        return self._get((p1, p2), "catT" if transposed else "cat", make)
 
     def catvec(self, p1: torch.Tensor, p2: torch.Tensor) -> torch.Tensor:
-        return self._get2(p1, p2, "catv", lambda: torch.cat([p1.detach(), p2.detach()]).float().contiguous())
+        return self._get((p1, p2), "catv", lambda: (torch.cat([p1.detach(), p2.detach()]).float().contiguous(), None))
 
     def scaled(self, w: torch.Tensor, gamma: torch.Tensor, transposed: bool = False) -> torch.Tensor:
         """Operand of a Linear with layer scale folded in: gamma (.) W row-wise, (N, K), or its (K, N) transpose.  Derived from two
         masters, so it is re-made when either changed (after an optimizer step) instead of by the batched refresh."""
         def make():
             ws = (w.detach().reshape(w.shape[0], -1) * gamma.detach().view(-1, 1)).contiguous()
-            return K.cast_transpose_bf16(ws) if transposed else K.cast_bf16(ws)
-        return self._get2(w, gamma, "lsT" if transposed else "ls", make)
+            return K.cast_transpose_bf16(ws) if transposed else K.cast_bf16(ws), None
+        return self._get((w, gamma), "lsT" if transposed else "ls", make)
 
     def scaled_vec(self, b: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
-        return self._get2(b, gamma, "lsv", lambda: (b.detach() * gamma.detach()).float().contiguous())
+        return self._get((b, gamma), "lsv", lambda: ((b.detach() * gamma.detach()).float().contiguous(), None))
 
     def vec16(self, p: torch.Tensor) -> torch.Tensor:
-        return self._get(p, "v", lambda: K.cast_bf16(p.detach().contiguous()), None if K.EXACT else (0, 1, p.numel(), 0))
+        return self._get((p,), "v", lambda: (K.cast_bf16(p.detach().contiguous()), None if K.EXACT else [CastPiece(0, 0, 0, 1, p.numel(), 0)]))
 
     def relpos(self, table: torch.Tensor, ws: int) -> torch.Tensor:
         """Expanded relative-position bias (nH, NP, NP) fp32 of a window-attention module (the kernels' `bias_q`; query-major, scaled by
@@ -138,70 +158,51 @@ class ParamCache:
         launches of ~9 us per Swin-L step otherwise).  Verification mode: the fp32 kernels index the table themselves."""
         if K.EXACT:
             return table.detach()
-        ok = table.dtype == F32 and table.is_contiguous()
-        return self._get(table, ("relpos", ws), lambda: K.relpos_expand(table.detach().contiguous(), ws)[0],
-                         ("relpos", ws, table.shape[1]) if ok else None)
+        def make():
+            ok = table.dtype == F32 and table.is_contiguous()
+            return K.relpos_expand(table.detach().contiguous(), ws)[0], RelposPlan(ws, table.shape[1]) if ok else None
+        return self._get((table,), ("relpos", ws), make)
+
+    def _build_tables(self) -> RefreshTables:
+        casts = [(e, pc) for e in self._store.values() if isinstance(e.plan, list) for pc in e.plan]
+        rels = [e for e in self._store.values() if isinstance(e.plan, RelposPlan)]
+        dev = next(iter(self._store.values())).operand.device
+        cast = np.zeros(len(casts), dtype=self._CAST)
+        cast["src"] = [e.owners[pc.owner]().data_ptr() + pc.src_off for e, pc in casts]
+        cast["dst"] = [e.operand.data_ptr() + 2 * pc.dst_off for e, pc in casts]
+        for f in ("rows", "cols", "tr"):
+            cast[f] = [getattr(pc, f) for _, pc in casts]
+        cast["tc"] = -(-cast["cols"] // 64)
+        tiles = -(-cast["rows"].astype(np.int64) // 64) * cast["tc"]
+        cast["tb"] = np.cumsum(tiles) - tiles                       # first 64 x 64 tile of each piece
+        rel = np.zeros(len(rels), dtype=self._RELPOS)
+        rel["table"] = [e.owners[0]().data_ptr() for e in rels]
+        rel["bias_q"] = [e.operand.data_ptr() for e in rels]
+        rel["nH"] = [e.plan.nH for e in rels]
+        rel["ws"] = [e.plan.ws for e in rels]
+        rel["NP"] = [e.operand.shape[-1] for e in rels]
+        blocks = -(-(rel["nH"].astype(np.int64) * rel["NP"] * rel["NP"]) // 2048)
+        rel["blk_begin"] = np.cumsum(blocks) - blocks
+        return RefreshTables(K.upload_table(cast, dev, pinned=False) if casts else None, len(casts), int(tiles.sum()),
+                             K.upload_table(rel, dev, pinned=False) if rels else None, len(rels), int(blocks.sum()))
 
     def refresh(self):
         """Re-cast every cached operand copy from its (updated) fp32 master, in one launch."""
-        import numpy as np
-        from .capi import check, lib, stream_ptr
         WGRADS.reset()                              # start of a step: nothing of an earlier (failed) backward may survive
-        if not self._store:
-            return
-        dead = [k for k, e in self._store.items() if e[3]() is None or e[4] is None or e[3]().data_ptr() != e[1]
-                or (len(e) > 5 and (e[5]() is None or e[5]().data_ptr() != e[0][3]))]
-        for k in dead:                              # padded / special entries and moved storages are re-made lazily
+        # padded / special entries (no plan), dead owners and moved storages are dropped and re-made lazily
+        dead = [k for k, e in self._store.items() if e.plan is None or e.moved()]
+        for k in dead:
             del self._store[k]
             self._table = None
         if not self._store:
             return
-        if self._table is None:
-            pieces, keys, dev = [], [], None
-            rel = []                                            # (table ptr, bias ptr, nH, ws, NP) of the expanded relative-position biases
-            for k, e in self._store.items():
-                if isinstance(e[4], tuple) and e[4] and e[4][0] == "relpos":
-                    rel.append((e[1], e[2].data_ptr(), e[4][2], e[4][1], e[2].shape[-1]))
-                    keys.append(k)
-                    dev = e[2].device
-                    continue
-                if isinstance(e[4], list):                      # an operand stacked from two masters: one piece per master
-                    for src, doff, rows, cols, tr in e[4]:
-                        pieces.append((src, e[2].data_ptr() + 2 * doff, rows, cols, tr))
-                else:
-                    off, rows, cols, tr = e[4]
-                    pieces.append((e[1] + off, e[2].data_ptr(), rows, cols, tr))
-                keys.append(k)
-                dev = e[2].device
-            desc = np.zeros(len(pieces), dtype=[("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"),
-                                                ("tr", "<i4"), ("tc", "<i4"), ("tb", "<i8")])
-            tb = 0
-            for i, (src, dst, rows, cols, tr) in enumerate(pieces):
-                desc[i] = (src, dst, rows, cols, tr, -(-cols // 64), tb)
-                tb += -(-rows // 64) * -(-cols // 64)
-            tab = K.upload_table(desc, dev, pinned=False) if len(pieces) else None
-            rtab, rblocks = None, 0
-            if rel:
-                rdesc = np.zeros(len(rel), dtype=[("table", "<u8"), ("bias_q", "<u8"), ("bias_k", "<u8"), ("nH", "<i4"), ("ws", "<i4"),
-                                                  ("NP", "<i4"), ("blk_begin", "<i4")])
-                for i, (tp, bp, nH, ws, NP) in enumerate(rel):
-                    rdesc[i] = (tp, bp, 0, nH, ws, NP, rblocks)
-                    rblocks += -(-(nH * NP * NP) // 2048)
-                rtab = K.upload_table(rdesc, dev, pinned=False)
-            keys = (keys, len(pieces))
-            self._table = (tab, keys[1], tb, keys[0], rtab, len(rel), rblocks)
-        tab, n, total, keys, rtab, rn, rblocks = self._table
-        if n:
-            check(lib.uenc_cast_multi(tab.data_ptr(), n, total, stream_ptr()), "cast_multi")
-        if rn:
-            check(lib.uenc_relpos_expand_grouped(rtab.data_ptr(), rn, rblocks, stream_ptr()), "relpos_expand_grouped")
-        for k in keys:
-            e = self._store[k]
-            if len(e) > 5:
-                p1, p2 = e[3](), e[5]()
-                self._store[k] = ((p1._version, p1.data_ptr(), p2._version, p2.data_ptr()), e[1], e[2], e[3], e[4], e[5])
-            else:
-                self._store[k] = (e[3]()._version, e[1], e[2], e[3], e[4])
+        t = self._table = self._table or self._build_tables()
+        if t.ncast:
+            check(lib.uenc_cast_multi(t.cast.data_ptr(), t.ncast, t.tiles, stream_ptr()), "cast_multi")
+        if t.nrelpos:
+            check(lib.uenc_relpos_expand_grouped(t.relpos.data_ptr(), t.nrelpos, t.blocks, stream_ptr()), "relpos_expand_grouped")
+        for e in self._store.values():              # every entry left is up to date with its owners' current versions
+            e.sig = tuple([(ref()._version, ptr) for ref, (_, ptr) in zip(e.owners, e.sig)])
 
 
 CACHE = ParamCache()
@@ -254,6 +255,38 @@ def _bias_pad(b: Optional[torch.Tensor], Np: int) -> Optional[torch.Tensor]:
     return torch.nn.functional.pad(b.detach(), (0, Np - b.numel()))
 
 
+def _token_split(M: int, guess: int) -> Tuple[int, int]:
+    """M rows cut into about `guess` equal token ranges of whole 64-row k-steps -> (mlen, nsplit): rows per range, ranges."""
+    mlen = -(-(-(-M // 64)) // guess) * 64
+    return mlen, -(-M // mlen)
+
+
+@dataclasses.dataclass(slots=True)
+class WgradWork:
+    """One dw += alpha dy^T x (db += alpha column sums of dy) of a grouped launch: the fields the two C descriptors share, under the
+    structs' own names, and what the queue keeps next to them."""
+    dy: int; x: int; dw: int; db: int                         # pointers; db 0: no bias gradient
+    ldy: int; ldx: int; ldw: int
+    M: int; N: int; K: int
+    dy_f32: int; x_f32: int                                   # (read by the register-staged kernel only)
+    tiles_k: int; mlen: int; nsplit: int
+    items: int                  # work items: output tiles x k tiles x token ranges
+    keep: tuple                 # the tensors behind the four pointers, alive until the launch
+    device: torch.device
+    store: int                  # 0: added atomically; 1: dw and db stored; 2: dw stored, db added (single token range only)
+    alpha: float
+
+    @classmethod
+    def of(cls, dy, x, dw, db, tile: int, guess: int, store: int = 0, alpha: float = 1.0):
+        """The problem on 2-D operands dy (M, N), x (M, K), dw (N, K), db (N) | None with `tile` x `tile` output tiles."""
+        M, N, Kd = dy.shape[0], dy.shape[1], x.shape[1]
+        mlen, nsplit = _token_split(M, guess)
+        tiles_k = -(-Kd // tile)
+        return cls(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else 0, dy.stride(0), x.stride(0), dw.stride(0),
+                   M, N, Kd, int(dy.dtype == F32), int(x.dtype == F32), tiles_k, mlen, nsplit, -(-N // tile) * tiles_k * nsplit,
+                   (dy, x, dw, db), dy.device, store, float(alpha))
+
+
 class WgradQueue:
     """Deferred weight-gradient GEMMs, launched as groups.
 
@@ -277,30 +310,29 @@ class WgradQueue:
     # 256 KB-per-tile float-atomic bursts of the epilogue at the chip's 1.3 TB/s.  Bias gradients stay accumulated (other kernels
     # add to them too, e.g. the window-attention backward's padding-slot share of qkv.bias).
     fresh = False
+    enabled = True
     FLUSH_ITEMS = {256: 4096, 128: 16384}        # ~16 / 32 waves of workgroups per launch (bigger groups measured a little faster;
                                                  # flushing only at the end of backward would stall the gradient all-reduce overlap)
     TOKENS_PER_ITEM = {256: 16384, 128: 4096}     # token range of one work item (128 / 64 k-steps of 64)
 
     def __init__(self):
-        ev = os.environ.get("UENC_WGRAD_FLUSH")
-        if ev:                                   # A/B knob: items of the 256-tile class per launch (the 128-tile class gets 4x)
-            self.FLUSH_ITEMS = {256: int(ev), 128: 4 * int(ev)}
-        self.pending = {256: [], 128: []}        # tile -> [(desc tuple without item_begin, items, keepalive)]
+        self._empty()
+
+    def _empty(self):
+        self.pending = {256: [], 128: []}        # tile -> [WgradWork]
         self.items = {256: 0, 128: 0}
-        self.small = []                          # descriptors for the register-staged kernel (small / fp32-operand problems)
+        self.small = []                          # [WgradWork] for the register-staged kernel (small / fp32-operand problems)
         self.small_items = 0
         self.notify = []
         self.post = []                           # steps that read a queued group's result (layer-scale gradients): run by flush()
         self.callback_armed = False
-        self.enabled = True
         self.written = set()                     # data_ptr of gradient buffers that received a contribution this step
-        self.stores = {}                         # data_ptr -> store flag of a queued, not yet launched "store" descriptor
+        self.stores = {}                         # data_ptr -> the queued, not yet launched WgradWork that STORES into that buffer
 
     def overlap_exchange(self):
         """Data parallel: launch smaller groups (about 4 waves of workgroups), so that the backbone's weight gradients become final
         -- and their buckets' all-reduce starts -- stage by stage instead of in one group at the end of the backward pass."""
-        if not os.environ.get("UENC_WGRAD_FLUSH"):
-            self.FLUSH_ITEMS = {256: 1024, 128: 4096}
+        self.FLUSH_ITEMS = {256: 1024, 128: 4096}
 
     @staticmethod
     def eligible(dy, x, gw) -> bool:
@@ -320,17 +352,10 @@ class WgradQueue:
 
     def add_small(self, dy, x, gw, gb, notify=(), alpha: float = 1.0):
         """Queue a problem for the grouped register-staged kernel (launched with the others at flush time)."""
-        M, N, Kd = dy.shape[0], dy.shape[1], x.shape[1]
-        mt = -(-M // 64)
-        nsplit = max(1, min(mt // 8, -(-M // 2048)))
-        mlen = -(-mt // nsplit) * 64
-        nsplit = -(-M // mlen)
-        tiles_k = -(-Kd // 128)
-        items = -(-N // 128) * tiles_k * nsplit
-        self.small.append(((dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb.data_ptr() if gb is not None else 0,
-                            dy.stride(0), x.stride(0), gw.stride(0), M, N, Kd, int(dy.dtype == F32), int(x.dtype == F32), tiles_k, mlen,
-                            nsplit), items, (dy, x, gw, gb), float(alpha)))
-        self.small_items += items
+        M = dy.shape[0]
+        w = WgradWork.of(dy, x, gw, gb, 128, max(1, min(-(-M // 64) // 8, -(-M // 2048))), alpha=alpha)
+        self.small.append(w)
+        self.small_items += w.items
         self.notify.extend(p for p in notify if p is not None)
         self._arm()
         if not self.callback_armed or self.small_items >= 4096:
@@ -352,38 +377,38 @@ class WgradQueue:
         # 256 x 256 tiles re-read the operands half as often as 128 x 128 ones; they win unless padding N, K up to 256 wastes too much
         pad = lambda t: (-(-N // t) * t) * (-(-Kd // t) * t)
         tile = 256 if pad(256) <= 1.3 * pad(128) else 128
-        nsplit = max(1, -(-M // self.TOKENS_PER_ITEM[tile]))
-        mlen = -(-(M // 64) // nsplit) * 64
-        nsplit = -(-M // mlen)
-        tiles_k = -(-Kd // tile)
-        items = -(-N // tile) * tiles_k * nsplit
-        store = [2 if (self.fresh and nsplit == 1 and first) else 0]      # mutable: a later contribution to the same buffer clears it
-        if store[0]:
-            self.stores[gw.data_ptr()] = store
-        self.pending[tile].append(((dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb.data_ptr() if gb is not None else 0,
-                                    dy.stride(0), x.stride(0), gw.stride(0), M, N, Kd, tiles_k, mlen, nsplit), items, (dy, x, gw, gb), store,
-                                   float(alpha)))
-        self.items[tile] += items
+        w = WgradWork.of(dy, x, gw, gb, tile, max(1, -(-M // self.TOKENS_PER_ITEM[tile])), alpha=alpha)
+        if self.fresh and w.nsplit == 1 and first:
+            w.store = 2                                                   # a later contribution to the same buffer clears it (touch)
+            self.stores[gw.data_ptr()] = w
+        self.pending[tile].append(w)
+        self.items[tile] += w.items
         self.notify.extend(p for p in notify if p is not None)
         self._arm()
         if not self.callback_armed or self.items[tile] >= self.FLUSH_ITEMS[tile]:
             self.flush()
 
     @classmethod
-    def launch(cls, tile: int, descs, device):
-        """descs: [(dy_ptr, x_ptr, dw_ptr, db_ptr, ldy, ldx, ldw, M, N, K, tiles_k, mlen, nsplit, items, store[, alpha])]."""
-        import numpy as np
-        from .capi import check, lib, stream_ptr
-        desc = np.zeros(len(descs), dtype=cls._DESC)
-        begin, flops, nbytes = 0, 0.0, 0.0
-        for i, d in enumerate(descs):
-            desc[i] = d[:13] + (begin, d[14], d[15] if len(d) > 15 else 1.0, 0)
-            begin += d[13]
-            flops += 2.0 * d[7] * d[8] * d[9]
-            nbytes += 2.0 * d[7] * (d[8] + d[9]) + 4.0 * d[8] * d[9]           # bf16 operands read once + the fp32 gradient written once
-        tab = K.upload_table(desc, device)
+    def launch(cls, tile: int, works: Sequence[WgradWork], device):
+        """One grouped LDS-DMA launch (bf16 operands, `tile` x `tile` output tiles) of `works`, in that order."""
+        tab, items = K.pack_table(cls._DESC, works, [w.items for w in works], "item_begin")
+        flops, nbytes = 0.0, 0.0
+        for w in works:
+            flops += 2.0 * w.M * w.N * w.K
+            nbytes += 2.0 * w.M * (w.N + w.K) + 4.0 * w.N * w.K               # bf16 operands read once + the fp32 gradient written once
+        dev = K.upload_table(tab, device)
         lib.uenc_prof_next_bytes(nbytes)
-        check(lib.uenc_gemm_tn_grouped(tab.data_ptr(), len(descs), begin, tile, flops, stream_ptr()), "gemm_tn_grouped")
+        check(lib.uenc_gemm_tn_grouped(dev.data_ptr(), len(works), items, tile, flops, stream_ptr()), "gemm_tn_grouped")
+
+    @classmethod
+    def launch_small(cls, works: Sequence[WgradWork], device):
+        """One grouped launch of the register-staged kernel (fp32 or bf16 operands, ragged M)."""
+        tab, items = K.pack_table(cls._DESC_SMALL, works, [w.items for w in works], "item_begin")
+        flops = 0.0
+        for w in works:
+            flops += 2.0 * w.M * w.N * w.K
+        check(lib.uenc_gemm_tn_grouped_small(K.upload_table(tab, device).data_ptr(), len(works), items, flops, stream_ptr()),
+              "gemm_tn_grouped_small")
 
     def _end_of_backward(self):
         self.callback_armed = False
@@ -392,13 +417,8 @@ class WgradQueue:
     def reset(self):
         """Drop whatever a previous, FAILED backward left queued (the engine skips its final callbacks when a node raises, so
         `callback_armed` would stay set and the stale groups would be launched -- a step late -- with the next pass)."""
-        self.pending = {256: [], 128: []}
-        self.items = {256: 0, 128: 0}
-        self.small, self.small_items, self.notify, self.post = [], 0, [], []
+        self._empty()
         SMALLQ.clear()
-        self.callback_armed = False
-        self.written = set()
-        self.stores = {}
         self.fresh = False
 
     def touch(self, gw) -> bool:
@@ -407,9 +427,9 @@ class WgradQueue:
         key = gw.data_ptr()
         first = key not in self.written
         self.written.add(key)
-        st = self.stores.pop(key, None)
-        if st is not None:
-            st[0] = 0
+        queued = self.stores.pop(key, None)
+        if queued is not None:
+            queued.store = 0
         return first
 
     def flush(self):
@@ -417,25 +437,15 @@ class WgradQueue:
         gradient-ready notifications."""
         self.stores = {}
         for tile in (256, 128):
-            ent = self.pending[tile]
-            if not ent:
+            works = self.pending[tile]
+            if not works:
                 continue
-            ent.sort(key=lambda e: -e[0][11])                       # longest token ranges first
-            self.launch(tile, [d + (items, st[0], al) for d, items, _, st, al in ent], ent[0][2][0].device)
+            works.sort(key=lambda w: -w.mlen)                       # longest token ranges first
+            self.launch(tile, works, works[0].device)
             self.pending[tile] = []
             self.items[tile] = 0
         if self.small:
-            import numpy as np
-            from .capi import check, lib, stream_ptr
-            desc = np.zeros(len(self.small), dtype=self._DESC_SMALL)
-            begin, flops = 0, 0.0
-            for i, (d, items, _, al) in enumerate(self.small):
-                desc[i] = d + (begin, al)
-                begin += items
-                flops += 2.0 * d[7] * d[8] * d[9]
-            dev = self.small[0][2][0].device
-            tab = K.upload_table(desc, dev)
-            check(lib.uenc_gemm_tn_grouped_small(tab.data_ptr(), len(self.small), begin, flops, stream_ptr()), "gemm_tn_grouped_small")
+            self.launch_small(self.small, self.small[0].device)
             self.small = []
             self.small_items = 0
         if SMALLQ:
@@ -452,14 +462,12 @@ class WgradQueue:
 WGRADS = WgradQueue()
 
 # Small parameter-gradient reductions (LayerNorm dgamma / dbeta block partials, relative-position-table partials) parked during the backward
-# pass and summed by one grouped launch per kind when the weight-gradient queue is flushed (K.SmallReductions).  UENC_DEFER_SMALL=0: every
-# pass reduces its own partials, as before (A/B).
+# pass and summed by one grouped launch per kind when the weight-gradient queue is flushed (K.SmallReductions).
 SMALLQ = K.SmallReductions()
-_DEFER_SMALL = os.environ.get("UENC_DEFER_SMALL", "1") != "0"
 
 
 def _defer():
-    return SMALLQ if (_DEFER_SMALL and WGRADS.enabled and not K.EXACT) else None
+    return SMALLQ if (WGRADS.enabled and not K.EXACT) else None
 
 
 def _after_deferred():
@@ -470,25 +478,17 @@ def _after_deferred():
             WGRADS.flush()
 
 
-def _ln_bwd(*a, **k):
-    k.setdefault("defer", _defer())
-    r = K.layernorm_bwd(*a, **k)
-    _after_deferred()
-    return r
+def _deferring(kernel: str, needs: Optional[str] = None):
+    """The backward wrapper K.<kernel> with its parameter-gradient partials parked (only when argument `needs` is given, if named)."""
+    def run(*a, **k):
+        k.setdefault("defer", _defer() if needs is None or k.get(needs) is not None else None)
+        r = getattr(K, kernel)(*a, **k)
+        _after_deferred()
+        return r
+    return run
 
 
-def _pm_ln_bwd(*a, **k):
-    k.setdefault("defer", _defer())
-    r = K.patch_merge_ln_bwd(*a, **k)
-    _after_deferred()
-    return r
-
-
-def _wattn_bwd(*a, **k):
-    k.setdefault("defer", _defer() if k.get("dtable") is not None else None)
-    r = K.window_attn_bwd(*a, **k)
-    _after_deferred()
-    return r
+_ln_bwd, _pm_ln_bwd, _wattn_bwd = _deferring("layernorm_bwd"), _deferring("patch_merge_ln_bwd"), _deferring("window_attn_bwd", "dtable")
 
 
 def begin_step(fresh_grads: bool = False):
@@ -1449,10 +1449,7 @@ class MaskHeadsFn(torch.autograd.Function):
         elif ctx.needs_input_grad[0]:
             dmf = torch.empty((B, HW, C), dtype=F32, device=dev)
             tile = 256 if C % 256 == 0 else 128
-            tiles_k = -(-C // tile)
-            items = -(-HW // tile) * tiles_k
-            WgradQueue.launch(tile, [(D[b].data_ptr(), ME[b].data_ptr(), dmf[b].data_ptr(), 0, D.stride(1), C, C, Mp, HW, C, tiles_k, Mp, 1, items, 1)
-                                     for b in range(B)], dev)
+            WgradQueue.launch(tile, [WgradWork.of(D[b], ME[b], dmf[b], None, tile, 1, store=1) for b in range(B)], dev)   # one token range
         return (dmf, None, None) + tuple(torch.stack([dme[b][h * Q:(h + 1) * Q] for b in range(B)]).to(mes[h].dtype) for h in range(n))
 
 
@@ -1530,8 +1527,8 @@ def _conv_wmat(weight, tag, transposed=False, pad8=False):
         if pad8:
             w = F.pad(w, (0, -w.shape[1] % 8, 0, -w.shape[0] % 8))
         w = w.contiguous()
-        return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w)
-    return CACHE._get(weight, tag + "t" if transposed else tag, make)
+        return K.cast_transpose_bf16(w) if transposed else K.cast_bf16(w), None
+    return CACHE._get((weight,), tag + "t" if transposed else tag, make)
 
 
 def _conv_dy(dy, M, Co):
@@ -1563,15 +1560,9 @@ class Conv3x3Fn(torch.autograd.Function):
     @staticmethod
     def _wgrad_gemm(dy2, col, dw, db):
         M, Co = dy2.shape
-        Kd = col.shape[1]
         if M % 64 == 0 and Co % 8 == 0 and not K.EXACT:
             tile = 256 if Co % 256 == 0 else 128
-            nsplit = max(1, M // 16384)
-            mlen = -(-(M // 64) // nsplit) * 64
-            nsplit = -(-M // mlen)
-            tiles_k = -(-Kd // tile)
-            WgradQueue.launch(tile, [(dy2.data_ptr(), col.data_ptr(), dw.data_ptr(), 0, Co, Kd, Kd, M, Co, Kd, tiles_k, mlen,
-                                      nsplit, -(-Co // tile) * tiles_k * nsplit, 0)], dy2.device)
+            WgradQueue.launch(tile, [WgradWork.of(dy2, col, dw, None, tile, max(1, M // 16384))], dy2.device)
         else:
             K.gemm_tn(dy2, col, dw, None)
 
