@@ -643,6 +643,29 @@ int uenc_bn_act_bwd_apply(const void* dy, int dy_dtype, const void* y, int y_dty
                           const float* var, const float* gamma, const float* sums, void* dx, int dx_dtype, void* dres, int dres_dtype, long M,
                           int C, float eps, int relu, int train, uenc_stream_t stream);
 
+/* ---- training targets from a panoptic id map (csrc/targets.hip; uenc.modeling.targets.build_targets) -----------------------------------------
+ * One padded batch: pan (B, H, W) int32 segment ids; sizes (B, 2) = each image's own (h, w) <= (H, W), pixels outside it belong to no
+ * segment whatever pan holds there; the segment table is one row of UENC_TARGETS_MAX_SEGMENTS entries per image, seg_ids (B, 256) int32
+ * with n_seg (B) of them in use.  Ids are any int32 > 0 (an entry <= 0 matches nothing; of two equal ids the lower row is the pixel's row);
+ * an id of the map that the table does not list has no row.  All pointers are DEVICE memory, all tables int32; B <= 65535 and
+ * H * W < 2^31 - 4096.  Values that index memory (n_seg, sizes, slot, plane0, T) are clamped or made inert on the device, never trusted.
+ * Each call is one launch, whatever n_seg is; no float arithmetic, the same input gives the same bits. */
+#define UENC_TARGETS_MAX_SEGMENTS 256
+/* area (B, 256) int32, ZERO-FILLED by the caller: area[b, r] += the number of pixels of image b, inside its own size, whose row is r
+ * (counted in LDS; one integer atomic add per workgroup and row). */
+int uenc_targets_area(const int* pan, const int* sizes, const int* seg_ids, const int* n_seg, int* area, int B, int H, int W,
+                      uenc_stream_t stream);
+/* slot (B, 256): the target plane of a row inside its image, or -1 (several rows may share a plane); cls (B, 256): the class a row writes
+ * into the label map, or < 0; plane0 (B), T (B): image b owns planes plane0[b] .. plane0[b] + T[b] - 1 of masks (total_planes, H, W)
+ * uint8, T[b] <= 256 (an image whose planes do not lie inside [0, total_planes) gets none; a slot outside [0, T[b]) counts as -1).
+ *   masks[plane0[b] + t, y, x] = 1 where the pixel's row has slot t, else 0
+ *   sem_seg[b, y, x] (int64)   = cls of the pixel's row; ignore_label where there is no row, where cls < 0, and in the padding
+ * Every byte of sem_seg and of the planes the images own is written exactly once (nothing needs zeroing), with 16-byte stores when
+ * H * W % 16 == 0 and pan, masks and sem_seg are 16-byte aligned. */
+int uenc_targets_write(const int* pan, const int* sizes, const int* seg_ids, const int* n_seg, const int* slot, const int* cls,
+                       const int* plane0, const int* T, long long ignore_label, unsigned char* masks, long long* sem_seg, int B, int H, int W,
+                       int total_planes, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

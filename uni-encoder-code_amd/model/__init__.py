@@ -19,6 +19,7 @@ from uenc.evaluation import InstanceSegEvaluator  # noqa: F401  (train_net.py:55
 _sys.modules[__name__ + ".modeling"] = modeling
 _sys.modules[__name__ + ".modeling.matcher"] = modeling.matcher
 _sys.modules[__name__ + ".modeling.criterion"] = modeling.criterion
+_sys.modules[__name__ + ".modeling.targets"] = modeling.targets
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
 _sys.modules[__name__ + ".modeling.pixel_decoder"] = modeling.pixel_decoder
 _sys.modules[__name__ + ".modeling.pixel_decoder.fpn"] = modeling.pixel_decoder.fpn

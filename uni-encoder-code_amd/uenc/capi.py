@@ -148,6 +148,9 @@ _SIGNATURES = {
     "uenc_bn_act_fwd": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_f, c_i, c_p],
     "uenc_bn_act_bwd_reduce": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_l, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_l, c_p],
     "uenc_bn_act_bwd_apply": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_f, c_i, c_i, c_p],
+    # training targets from a panoptic id map (csrc/targets.hip)
+    "uenc_targets_area": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "uenc_targets_write": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
 }
 
 

@@ -122,6 +122,15 @@ def read_sequence_image(file_name: str, format: Optional[str] = None, dataset: s
     return arr
 
 
+def rgb2id(color):
+    """panopticapi.utils.rgb2id [not in reference; the mapper imports it at :348]: the segment id r + 256 g + 65536 b of a panoptic PNG.
+    An (h, w, 3) array gives an (h, w) int32 id map (ids up to 2^24 - 1), a single colour gives an int."""
+    if isinstance(color, np.ndarray) and color.ndim == 3:
+        c = color.astype(np.int32)
+        return c[:, :, 0] + 256 * c[:, :, 1] + 65536 * c[:, :, 2]
+    return int(color[0]) + 256 * int(color[1]) + 65536 * int(color[2])
+
+
 def check_image_size(dataset_dict: dict, image: np.ndarray):
     """detection_utils.check_image_size: the file must have the size the dataset dict states (and the dict gets it if absent)."""
     if "width" in dataset_dict or "height" in dataset_dict:

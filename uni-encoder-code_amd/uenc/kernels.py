@@ -1211,6 +1211,50 @@ def crit_class_loss(call: CritCall, row_ind, col_ind, eos_coef: float):
     return loss, grad
 
 
+# ---- training targets from a panoptic id map (csrc/targets.hip) --------------------------------------------------------------------------------
+TARGETS_MAX_SEGMENTS = 256
+
+
+def _targets_table(pan, table, B):
+    """The batch (B, H, W) and its packed int32 table: seg_ids (B, 256), n_seg (B), sizes (B, 2) as one buffer of B * 259 entries (one
+    upload) -> the three views."""
+    _dev(pan, "pan", torch.int32, 3)
+    _dev(table, "table", torch.int32, 1)
+    S = TARGETS_MAX_SEGMENTS
+    if pan.shape[0] != B or table.numel() != B * (S + 3) or pan.shape[1] * pan.shape[2] >= 2 ** 31 - 4096:
+        raise capi.UencError(f"targets: pan (B, H, W) with H * W < 2^31 - 4096 and a table of B * {S + 3} entries are expected")
+    return table[:B * S], table[B * S:B * S + B], table[B * S + B:]
+
+
+def targets_area(pan: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """-> area (B, 256) int32: the pixels of every table row inside its image's own size.  pan (B, H, W) int32; table: seg_ids (B, 256),
+    n_seg (B), sizes (B, 2) packed in that order.  uenc_targets_area."""
+    B, H, W = pan.shape
+    ids, n_seg, sizes = _targets_table(pan, table, B)
+    area = torch.zeros((B, TARGETS_MAX_SEGMENTS), dtype=torch.int32, device=pan.device)
+    check(lib.uenc_targets_area(pan.data_ptr(), sizes.data_ptr(), ids.data_ptr(), n_seg.data_ptr(), area.data_ptr(), B, H, W, stream_ptr()),
+          "targets_area")
+    return area
+
+
+def targets_write(pan: torch.Tensor, table: torch.Tensor, plan: torch.Tensor, total_planes: int, ignore_label: int):
+    """-> masks (total_planes, H, W) uint8, sem_seg (B, H, W) int64.  plan: slot (B, 256), cls (B, 256), plane0 (B), T (B) int32 packed in
+    that order (one upload).  Neither output is zeroed first: the kernel writes every byte.  uenc_targets_write."""
+    B, H, W = pan.shape
+    ids, n_seg, sizes = _targets_table(pan, table, B)
+    _dev(plan, "plan", torch.int32, 1)
+    S = TARGETS_MAX_SEGMENTS
+    if plan.numel() != B * (2 * S + 2) or total_planes < 0:
+        raise capi.UencError(f"targets_write: a plan of B * {2 * S + 2} entries and total_planes >= 0 are expected")
+    masks = torch.empty((total_planes, H, W), dtype=torch.uint8, device=pan.device)
+    sem = torch.empty((B, H, W), dtype=torch.int64, device=pan.device)
+    slot, cls, plane0, T = plan[:B * S], plan[B * S:2 * B * S], plan[2 * B * S:2 * B * S + B], plan[2 * B * S + B:]
+    check(lib.uenc_targets_write(pan.data_ptr(), sizes.data_ptr(), ids.data_ptr(), n_seg.data_ptr(), slot.data_ptr(), cls.data_ptr(),
+                                 plane0.data_ptr(), T.data_ptr(), int(ignore_label), masks.data_ptr() if total_planes else 0, sem.data_ptr(),
+                                 B, H, W, total_planes, stream_ptr()), "targets_write")
+    return masks, sem
+
+
 # ---- MonodepthLoss: view synthesis + photometric loss (csrc/monodepth.hip) -----------------------------------------------------------------
 # slots of the 67-pointer descriptor of uenc_view_synth_fwd / _bwd (struct VsDesc)
 _VS = {"disp": 0, "cflow": 4, "mask": 12, "T": 20, "K": 21, "invK": 22, "src": 23, "color": 24, "sample": 25, "sample_ego": 26, "sample_cmp": 27,

@@ -11,5 +11,7 @@ from . import matcher
 from .matcher import HungarianMatcher
 from . import criterion
 from .criterion import SetCriterion, build_criterion
+from . import targets
+from .targets import build_targets, targets_from_instances
 from . import monodepth_loss
 from .monodepth_loss import MonodepthLoss

@@ -72,6 +72,13 @@ class OneFormer(nn.Module):
         # contiguous ids of the 'thing' classes (reference: MetadataCatalog.get(cfg.DATASETS.TRAIN[0]).thing_dataset_id_to_contiguous_id,
         # oneformer_model.py:124, 405); Cityscapes: classes 11..18.  Settable by the driver that knows the dataset.
         self.thing_ids = tuple(range(11, 19))
+        # the training criterion (uenc.modeling.criterion.SetCriterion); None: forward returns results in train mode as well
+        self.criterion = None
+
+    def set_criterion(self, criterion):
+        """The criterion of the training forward (a submodule from here on, as in Mask2Former); None takes it away again."""
+        self.criterion = criterion
+        return self
 
     @classmethod
     def from_config(cls, cfg):
@@ -130,7 +137,47 @@ class OneFormer(nn.Module):
         from . import kernels as K
         return K.upsample_bilinear(pred_masks.detach().float(), size)
 
+    @staticmethod
+    def _has_targets(x: dict) -> bool:
+        return "instances" in x or ("pan_seg" in x and "segments_info" in x)
+
+    def training_targets(self, seg: List[dict]):
+        """The criterion's targets of the segmentation dicts, at the padded image size: from "pan_seg" (an (h, w) integer id map) +
+        "segments_info" + "task" through build_targets (on the model's device: one synchronisation), or from "instances" (the
+        reference mapper's gt_classes / gt_masks) through targets_from_instances.  One kind per batch."""
+        from .modeling.targets import build_targets, targets_from_instances
+        d = max(int(self.size_divisibility), 1)
+        H = (max(x["left_image"].shape[-2] for x in seg) + d - 1) // d * d
+        W = (max(x["left_image"].shape[-1] for x in seg) + d - 1) // d * d
+        if all("pan_seg" in x and "segments_info" in x for x in seg):
+            maps = [torch.as_tensor(x["pan_seg"]).to(self.device) for x in seg]
+            # the label map and the texts have no consumer yet (no contrastive loss): no text is built
+            targets, _, _ = build_targets(maps, [x["segments_info"] for x in seg], [x["task"] for x in seg], thing_ids=self.thing_ids,
+                                          class_names=(), ignore_label=255, num_texts=0, size=(H, W))
+            return targets
+        if all("instances" in x for x in seg):
+            targets = targets_from_instances([x["instances"] for x in seg], (H, W))
+            return [{k: v.to(self.device) for k, v in t.items()} for t in targets]
+        raise ValueError('training_losses: every segmentation dict needs "pan_seg" + "segments_info", or every one "instances"')
+
+    def training_losses(self, batched_inputs: List[dict], point_draws=None):
+        """The training forward (reference tools/trainers/trainer_base.py:223, `loss_dict = self.model(data)`): targets, forward_features,
+        criterion.  -> {name: loss * weight_dict[name]} for the names the criterion's weight_dict knows, the others dropped (the
+        Detectron2 / Mask2Former convention: the trainer sums the values).  point_draws: see SetCriterion.forward."""
+        criterion = getattr(self, "criterion", None)
+        if criterion is None:
+            raise RuntimeError("training_losses: no criterion is set (OneFormer.set_criterion)")
+        if any(x["type"] != "segmentation" for x in batched_inputs):
+            raise ValueError('training_losses: only "segmentation" dicts have a loss; sequence dicts cannot be part of a training batch')
+        targets = self.training_targets(batched_inputs)
+        outputs, _ = self.forward_features(batched_inputs)
+        losses = criterion(outputs, targets, point_draws=point_draws)
+        return {k: v * criterion.weight_dict[k] for k, v in losses.items() if k in criterion.weight_dict}
+
     def forward(self, batched_inputs: List[dict]):
+        if self.training and getattr(self, "criterion", None) is not None and any(
+                x["type"] == "segmentation" and self._has_targets(x) for x in batched_inputs):
+            return self.training_losses(batched_inputs)
         results = []
         if any(e["type"] == "segmentation" for e in batched_inputs):
             results = self._forward_segmentation(batched_inputs)
