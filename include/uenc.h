@@ -666,6 +666,28 @@ int uenc_targets_write(const int* pan, const int* sizes, const int* seg_ids, con
                        const int* plane0, const int* T, long long ignore_label, unsigned char* masks, long long* sem_seg, int B, int H, int W,
                        int total_planes, uenc_stream_t stream);
 
+/* ---- depth decoder in training: the non-GEMM passes of TransDSSL (csrc/depth_head.hip) ----------------------------------------------------
+ * Channels-last maps, operands fp32 | bf16 by their dtype tag, arithmetic in fp32, every pointer 16-byte aligned.  No float atomics:
+ * each backward is a gather in a fixed order, two calls give the same bits. */
+/* y (B, 2H, 2W, C) = bilinear resize of x (B, H, W, C) with align_corners=True, C % 8 == 0: source = o * ((H - 1) / (2H - 1)) with the
+ * scale an fp32 division, i0 = floor, i1 = min(i0 + 1, H - 1) (F.interpolate's arithmetic); H == 1 or W == 1 copies along that axis. */
+int uenc_upsample2x_ac_fwd(const void* x, int x_dtype, void* y, int y_dtype, int B, int H, int W, int C, uenc_stream_t stream);
+/* dx (B, H, W, C), every element written = the adjoint applied to dy (B, 2H, 2W, C): each input cell gathers the outputs whose taps,
+ * recomputed with the forward's own expression, touch it (row-major order of the outputs). */
+int uenc_upsample2x_ac_bwd(const void* dy, int dy_dtype, void* dx, int dx_dtype, int B, int H, int W, int C, uenc_stream_t stream);
+/* Per row of C channels (C % 8 == 0, C <= 2048): res = a + b, g = res * softmax_c(z) (row maximum subtracted).  res and g share out_dtype. */
+int uenc_softmax_gate_fwd(const void* a, int a_dtype, const void* b, int b_dtype, const void* z, int z_dtype, void* res, void* g,
+                          int out_dtype, long P, int C, uenc_stream_t stream);
+/* att = softmax_c(z) recomputed;  d_res = dg * att + d_res_in (d_res_in NULL = 0),  d_z = att * (dg * res - sum_c(dg * res * att)).
+ * d_res is the gradient of a and of b alike; d_res and d_z share out_dtype. */
+int uenc_softmax_gate_bwd(const void* dg, int dg_dtype, const void* d_res_in, int d_res_in_dtype, const void* z, int z_dtype,
+                          const void* res, int res_dtype, void* d_res, void* d_z, int out_dtype, long P, int C, uenc_stream_t stream);
+/* disp (P) fp32 = sum_k softmax(z)_k * grid_k for z (P, D), grid (D) fp32; D % 8 == 0, D <= 64. */
+int uenc_soft_att_depth_fwd(const void* z, int z_dtype, const float* grid, float* disp, long P, int D, uenc_stream_t stream);
+/* dz_k = p_k * (grid_k - disp) * ddisp with p and disp recomputed from z; ddisp (P) fp32. */
+int uenc_soft_att_depth_bwd(const float* ddisp, const void* z, int z_dtype, const float* grid, void* dz, int dz_dtype, long P, int D,
+                            uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

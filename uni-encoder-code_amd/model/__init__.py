@@ -23,6 +23,9 @@ _sys.modules[__name__ + ".modeling.targets"] = modeling.targets
 _sys.modules[__name__ + ".modeling.monodepth_loss"] = modeling.monodepth_loss
 _sys.modules[__name__ + ".modeling.pixel_decoder"] = modeling.pixel_decoder
 _sys.modules[__name__ + ".modeling.pixel_decoder.fpn"] = modeling.pixel_decoder.fpn
+_sys.modules[__name__ + ".modeling.pixel_decoder.transdssl"] = modeling.pixel_decoder.transdssl
+_sys.modules[__name__ + ".modeling.pose_decoder"] = modeling.pose_decoder
+_sys.modules[__name__ + ".modeling.pose_decoder.resnet_like_pose_decoder"] = modeling.pose_decoder.resnet_like_pose_decoder
 _sys.modules[__name__ + ".modeling.backbone"] = modeling.backbone
 _sys.modules[__name__ + ".modeling.backbone.convnext"] = modeling.backbone.convnext
 _sys.modules[__name__ + ".modeling.backbone.resnet"] = modeling.backbone.resnet

@@ -151,6 +151,13 @@ _SIGNATURES = {
     # training targets from a panoptic id map (csrc/targets.hip)
     "uenc_targets_area": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "uenc_targets_write": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    # depth decoder in training: x2 align-corners upsample, softmax gate, soft-attention depth head (csrc/depth_head.hip)
+    "uenc_upsample2x_ac_fwd": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_upsample2x_ac_bwd": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_softmax_gate_fwd": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_p],
+    "uenc_softmax_gate_bwd": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_p],
+    "uenc_soft_att_depth_fwd": [c_p, c_i, c_p, c_p, c_l, c_i, c_p],
+    "uenc_soft_att_depth_bwd": [c_p, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_p],
 }
 
 

@@ -1,4 +1,4 @@
-"""Convolution layers of the "sequence" (depth / pose / motion) branch on the HIP GEMMs (inference).
+"""Convolution layers of the "sequence" (depth / pose / motion) branch on the HIP GEMMs: the inference path.
 
 The branch's decoders (reference model/modeling/pose_decoder/resnet_like_pose_decoder.py, motion_decoder/dynamo_motion_decoder_mod.py,
 pixel_decoder/transdssl.py) are plain conv nets: 1x1 and 3x3 (stride 1 / 2, padding 1) convolutions, eval-mode BatchNorm, ReLU / ELU,
@@ -7,7 +7,9 @@ gather (`uenc_im2col3x3`, `uenc_im2col3x3_s2`) + GEMM, with the bias, the eval-m
 bias: y = s * conv(x) + t) and a following ReLU in the GEMM epilogue.  Maps stay channels-last ((B, C, H, W)-shaped views of
 (B, H, W, C) storage) so the ATen resizes / concatenations between the layers copy nothing extra.
 
-Forward only (the reference drives this branch in eval mode only: train_net.py:283 asserts --eval-only and the branch has no loss).
+This module is forward only: it folds BatchNorm into detached, cached operands and refuses a BatchNorm in training mode.  The depth
+decoder (TransDSSL) and the pose decoder (ResNetLike) use it in eval() and take the autograd nodes of uenc/ops.py in train(); the two
+motion decoders (MotionDecoderV2) have no training path yet and run here only.
 """
 from typing import Optional
 

@@ -1556,3 +1556,86 @@ def bn_act_bwd(dy2: torch.Tensor, y2: Optional[torch.Tensor], x2: torch.Tensor, 
                                     var.data_ptr(), ptr(gamma), ptr(sums), dx.data_ptr(), dt(dx), ptr(dres), dt(dres) if want_dres else 0,
                                     M, C, float(eps), int(relu), int(train), stream_ptr()), "bn_act_bwd_apply")
     return dx, dres
+
+
+# ---- depth decoder in training: x2 align-corners upsample, softmax gate, soft-attention depth head (csrc/depth_head.hip) --------------
+def _dh_check(t: Optional[torch.Tensor], name: str, shape=None):
+    if t is None:
+        return None
+    if t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda or not t.is_contiguous():
+        raise capi.UencError(f"{name} must be a contiguous channels-last fp32 | bf16 GPU tensor, got {tuple(t.shape)} {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise capi.UencError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def upsample2x_ac_fwd(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """x (B, H, W, C) -> (B, 2H, 2W, C): bilinear, align_corners=True, F.interpolate's source coordinates."""
+    _dh_check(x, "x")
+    B, H, W, C = x.shape
+    y = torch.empty((B, 2 * H, 2 * W, C), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
+    check(lib.uenc_upsample2x_ac_fwd(x.data_ptr(), dt(x), y.data_ptr(), dt(y), B, H, W, C, stream_ptr()), "upsample2x_ac_fwd")
+    return y
+
+
+def upsample2x_ac_bwd(dy: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """dy (B, 2H, 2W, C) -> dx (B, H, W, C): the adjoint of upsample2x_ac_fwd as a gather (no atomics)."""
+    _dh_check(dy, "dy")
+    B, Ho, Wo, C = dy.shape
+    if Ho % 2 or Wo % 2:
+        raise capi.UencError(f"upsample2x_ac_bwd: dy must have even height and width, got {tuple(dy.shape)}")
+    dx = torch.empty((B, Ho // 2, Wo // 2, C), dtype=dy.dtype if out_dtype is None else out_dtype, device=dy.device)
+    check(lib.uenc_upsample2x_ac_bwd(dy.data_ptr(), dt(dy), dx.data_ptr(), dt(dx), B, Ho // 2, Wo // 2, C, stream_ptr()), "upsample2x_ac_bwd")
+    return dx
+
+
+def softmax_gate_fwd(a: torch.Tensor, b: torch.Tensor, z: torch.Tensor, out_dtype=torch.float32):
+    """a, b, z (..., C) -> (res = a + b, g = res * softmax over the last axis of z), both out_dtype."""
+    _dh_check(a, "a"), _dh_check(b, "b", a.shape), _dh_check(z, "z", a.shape)
+    C = a.shape[-1]
+    res = torch.empty(a.shape, dtype=out_dtype, device=a.device)
+    g = torch.empty_like(res)
+    check(lib.uenc_softmax_gate_fwd(a.data_ptr(), dt(a), b.data_ptr(), dt(b), z.data_ptr(), dt(z), res.data_ptr(), g.data_ptr(), dt(res),
+                                    a.numel() // max(C, 1), C, stream_ptr()), "softmax_gate_fwd")
+    return res, g
+
+
+def softmax_gate_bwd(dg: torch.Tensor, d_res_in: Optional[torch.Tensor], z: torch.Tensor, res: torch.Tensor, out_dtype=torch.float32):
+    """-> (d_res = dg * att + d_res_in, d_z = att * (dg * res - sum_c(dg * res * att))) with att = softmax(z) recomputed."""
+    _dh_check(dg, "dg"), _dh_check(d_res_in, "d_res_in", dg.shape), _dh_check(z, "z", dg.shape), _dh_check(res, "res", dg.shape)
+    C = dg.shape[-1]
+    d_res = torch.empty(dg.shape, dtype=out_dtype, device=dg.device)
+    d_z = torch.empty_like(d_res)
+    check(lib.uenc_softmax_gate_bwd(dg.data_ptr(), dt(dg), ptr(d_res_in), dt(d_res_in) if d_res_in is not None else 0, z.data_ptr(), dt(z),
+                                    res.data_ptr(), dt(res), d_res.data_ptr(), d_z.data_ptr(), dt(d_res), dg.numel() // max(C, 1), C,
+                                    stream_ptr()), "softmax_gate_bwd")
+    return d_res, d_z
+
+
+def _dh_grid(grid: torch.Tensor, D: int):
+    if grid.dtype != torch.float32 or not grid.is_cuda or not grid.is_contiguous() or grid.numel() != D:
+        raise capi.UencError(f"grid must be a contiguous fp32 GPU vector of {D} depth bins, got {tuple(grid.shape)} {grid.dtype}")
+
+
+def soft_att_depth_fwd(z: torch.Tensor, grid: torch.Tensor) -> torch.Tensor:
+    """z (..., D), grid (D) fp32 -> disp (...) fp32 = sum_k softmax(z)_k * grid_k."""
+    _dh_check(z, "z")
+    D = z.shape[-1]
+    _dh_grid(grid, D)
+    disp = torch.empty(z.shape[:-1], dtype=torch.float32, device=z.device)
+    check(lib.uenc_soft_att_depth_fwd(z.data_ptr(), dt(z), grid.data_ptr(), disp.data_ptr(), z.numel() // max(D, 1), D, stream_ptr()),
+          "soft_att_depth_fwd")
+    return disp
+
+
+def soft_att_depth_bwd(ddisp: torch.Tensor, z: torch.Tensor, grid: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
+    """ddisp (...) fp32, z (..., D) -> dz (..., D) out_dtype = p * (grid - disp) * ddisp, p and disp recomputed."""
+    _dh_check(z, "z")
+    D = z.shape[-1]
+    _dh_grid(grid, D)
+    if ddisp.dtype != torch.float32 or not ddisp.is_cuda or not ddisp.is_contiguous() or ddisp.numel() != z.numel() // max(D, 1):
+        raise capi.UencError(f"ddisp must be a contiguous fp32 GPU tensor with one value per row of z, got {tuple(ddisp.shape)} {ddisp.dtype}")
+    dz = torch.empty(z.shape, dtype=out_dtype, device=z.device)
+    check(lib.uenc_soft_att_depth_bwd(ddisp.data_ptr(), z.data_ptr(), dt(z), grid.data_ptr(), dz.data_ptr(), dt(dz), z.numel() // max(D, 1), D,
+                                      stream_ptr()), "soft_att_depth_bwd")
+    return dz

@@ -11,6 +11,11 @@ needed (csrc/postproc.hip).  `"type": "sequence"` inputs (`"left_image"` + `"lef
 of reference :306-365: two more passes of the accelerated backbone, the ego-pose decoder, the two motion decoders and the TransDSSL
 depth decoder (uenc/modeling/{pose_decoder,motion_decoder,pixel_decoder/transdssl}.py; channel counts hard-wired to Swin-T as in the
 reference), convolutions on the HIP GEMMs (uenc/convnet.py).
+
+Training: with a `SetCriterion` set (`set_criterion`) a batch of segmentation dicts with targets returns the segmentation loss dict
+(`training_losses`); with a `MonodepthLoss` set (`set_depth_criterion`) a batch made only of sequence dicts that carry the next frame
+returns `{"loss_monodepth": ...}` (`sequence_training_losses`), through the differentiable paths of the TransDSSL depth decoder and the
+ResNetLike pose decoder.  The two motion decoders stay inference-only.
 """
 from typing import List, Tuple
 
@@ -74,6 +79,13 @@ class OneFormer(nn.Module):
         self.thing_ids = tuple(range(11, 19))
         # the training criterion (uenc.modeling.criterion.SetCriterion); None: forward returns results in train mode as well
         self.criterion = None
+        # the criterion of the sequence branch's training forward (uenc.modeling.monodepth_loss.MonodepthLoss)
+        self.depth_criterion = None
+
+    def set_depth_criterion(self, loss):
+        """The MonodepthLoss of the sequence training forward (a submodule from here on); None takes it away again."""
+        self.depth_criterion = loss
+        return self
 
     def set_criterion(self, criterion):
         """The criterion of the training forward (a submodule from here on, as in Mask2Former); None takes it away again."""
@@ -174,7 +186,53 @@ class OneFormer(nn.Module):
         losses = criterion(outputs, targets, point_draws=point_draws)
         return {k: v * criterion.weight_dict[k] for k, v in losses.items() if k in criterion.weight_dict}
 
+    SEQUENCE_TRAINING_KEYS = ("left_image", "left_prev_image", "left_next_image", "K", "inv_K")
+
+    def sequence_training_losses(self, batched_inputs: List[dict], tie_noise=None):
+        """The training forward of the sequence branch -> what MonodepthLoss.forward returns, {"loss_monodepth": loss}.
+
+        The reference ships no trainer for this branch (train_net.py asserts --eval-only), so the composition is its own inference
+        composition (oneformer_model.py:306-365: backbone on the frames, pose decoder on the concatenated features of a frame pair,
+        depth decoder on the current frame's), extended by Monodepth2's convention for the second source frame: the pose of
+        (previous, current) is inverted (the reference's line), the pose of (current, next) is not.  Every dict carries the keys the
+        reference's depth_cityscapes_mapper.py emits; the photometric loss compares the un-colour-augmented frames (`orig_left_*`)
+        where they are present.  tie_noise: see MonodepthLoss.forward."""
+        from .modeling.geometry import transformation_from_parameters
+        crit = getattr(self, "depth_criterion", None)
+        if crit is None:
+            raise RuntimeError("sequence_training_losses: no depth criterion is set (OneFormer.set_depth_criterion)")
+        if crit.bool_CmpFlow or crit.bool_MotMask:
+            raise NotImplementedError("sequence_training_losses: bool_CmpFlow / bool_MotMask need the motion decoders, which are not "
+                                      "differentiable yet (MotionDecoderV2 is inference-only)")
+        if self.pose_decoder is None or self.sem_seg_head.depth_decoder is None:
+            raise NotImplementedError("this model was built without the sequence-branch decoders")
+        for x in batched_inputs:
+            for key in self.SEQUENCE_TRAINING_KEYS:
+                if key not in x:
+                    raise ValueError(f'sequence_training_losses: a sequence dict lacks "{key}"')
+        seq = batched_inputs
+        norm = lambda key: ImageList.from_tensors([(x[key].to(self.device) - self.pixel_mean) / self.pixel_std for x in seq], self.size_divisibility)
+        cur, prev, nxt = norm("left_image"), norm("left_prev_image"), norm("left_next_image")
+        f_cur, f_prev, f_next = self.backbone(cur.tensor), self.backbone(prev.tensor), self.backbone(nxt.tensor)
+        pair = lambda first, second: {k: torch.cat([first[k].float(), second[k].float()], dim=1) for k in f_cur}
+        outputs = {}
+        for frame, feats, invert in ((-1, pair(f_prev, f_cur), True), (1, pair(f_cur, f_next), False)):
+            axisangle, translation = self.pose_decoder(feats)
+            outputs[("cam_T_cam", 0, frame)] = transformation_from_parameters(axisangle[:, 0], translation[:, 0], invert=invert)
+        dummy_tasks = torch.zeros((cur.tensor.shape[0], self.task_mlp.layers[1].out_features), device=self.device)
+        _, depth = self.sem_seg_head(None, f_cur, dummy_tasks)
+        for s in range(4):
+            outputs[("disp", 0, s)] = depth[("disp", s)]
+        colour = lambda x, key: x.get("orig_" + key, x[key]).to(self.device).float() / 255
+        targets = [{("color", 0, 0): colour(x, "left_image"), ("color", -1, 0): colour(x, "left_prev_image"),
+                    ("color", 1, 0): colour(x, "left_next_image"),
+                    "K": torch.as_tensor(x["K"]).to(self.device).float(), "inv_K": torch.as_tensor(x["inv_K"]).to(self.device).float()} for x in seq]
+        return crit(outputs, targets, tie_noise=tie_noise)
+
     def forward(self, batched_inputs: List[dict]):
+        if (self.training and getattr(self, "depth_criterion", None) is not None and len(batched_inputs) > 0
+                and all(x["type"] == "sequence" and "left_next_image" in x for x in batched_inputs)):
+            return self.sequence_training_losses(batched_inputs)
         if self.training and getattr(self, "criterion", None) is not None and any(
                 x["type"] == "segmentation" and self._has_targets(x) for x in batched_inputs):
             return self.training_losses(batched_inputs)

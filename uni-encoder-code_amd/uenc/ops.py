@@ -581,8 +581,56 @@ def _as_bf16_operand(t2: torch.Tensor) -> torch.Tensor:
     return t2
 
 
-def _wgrad(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], rows=None):
-    """Accumulate dW (+ db) of out = x W^T + b into the parameters' .grad."""
+# Ordered weight gradients.  The grouped and split weight-gradient GEMMs add the products of their token ranges to dW with fp32 atomics,
+# in whatever order the workgroups finish: fast, and different in the last bits from run to run once a problem has more than one
+# range.  Layers run inside `ordered_wgrads()` (the flag is read in the forward and kept on the node) instead STORE each range's
+# product in a slab of its own -- one grouped launch, the same parallelism -- and sum the slabs in index order.
+_ORDERED = False
+_ORDERED_TOKENS = 16384                            # tokens per range: WgradQueue.TOKENS_PER_ITEM of the 256 x 256 tiles
+
+
+class ordered_wgrads:
+    def __enter__(self):
+        global _ORDERED
+        self.prev, _ORDERED = _ORDERED, True
+
+    def __exit__(self, *exc):
+        global _ORDERED
+        _ORDERED = self.prev
+
+
+def _tn_ordered(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: Optional[torch.Tensor]):
+    """gw += dy^T x, gb += column sums of dy, bit-reproducible: no float atomics between token ranges."""
+    M, N = dy.shape
+    Kd = x.shape[1]
+    n = -(-M // _ORDERED_TOKENS)
+    if n == 1:
+        K.gemm_tn(dy, x, gw, gb, splitm=1)                            # one token range: one contribution per element
+        return
+    cut = lambda t, i: t[i * _ORDERED_TOKENS:(i + 1) * _ORDERED_TOKENS]
+    if K.EXACT or not WgradQueue.eligible(dy, x, gw):
+        # operands the grouped kernel does not take (fp32, ragged M): the same slabs, one unsplit GEMM per token range
+        parts = torch.zeros((n, N, Kd), dtype=F32, device=dy.device)
+        pb = torch.zeros((n, N), dtype=F32, device=dy.device) if gb is not None else None
+        for i in range(n):
+            K.gemm_tn(cut(dy, i), cut(x, i), parts[i], None if pb is None else pb[i], splitm=1)
+        gw.add_(parts.sum(0))
+        if gb is not None:
+            gb.add_(pb.sum(0))
+        return
+    parts = torch.empty((n, N, Kd), dtype=F32, device=dy.device)
+    pb = torch.empty((n, N), dtype=F32, device=dy.device) if gb is not None else None
+    pad = lambda t: (-(-N // t) * t) * (-(-Kd // t) * t)
+    tile = 256 if pad(256) <= 1.3 * pad(128) else 128
+    works = [WgradWork.of(cut(dy, i), cut(x, i), parts[i], None if pb is None else pb[i], tile, 1, store=1) for i in range(n)]
+    WgradQueue.launch(tile, works, dy.device)
+    gw.add_(parts.sum(0))
+    if gb is not None:
+        gb.add_(pb.sum(0))
+
+
+def _wgrad(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], rows=None, ordered: bool = False):
+    """Accumulate dW (+ db) of out = x W^T + b into the parameters' .grad.  ordered: see `ordered_wgrads`."""
     if not w.requires_grad and (b is None or not b.requires_grad):
         return
     dy2, x2 = _as_bf16_operand(dy2), _as_bf16_operand(x2)
@@ -596,14 +644,19 @@ def _wgrad(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: Optional[tor
         if rows is not None:
             gb = gb[rows[0]:rows[1]]
     if N % 8 == 0 and Kd % 8 == 0 and gw.shape == (N, Kd):
-        _tn(dy2, x2, gw, gb, (w, b))
+        if ordered:
+            WGRADS.touch(gw)
+            _tn_ordered(dy2, x2, gw, gb)
+            _tn_notify(w, b)
+        else:
+            _tn(dy2, x2, gw, gb, (w, b))
         return
     # odd-sized tiny layers (class_embed N=20, task_mlp K=77): zero-padded scratch, then add the slice
     Np, Kp = -(-N // 8) * 8, -(-Kd // 8) * 8
     dyp, xp = _pad_cols(dy2), _pad_cols(x2)
     tw = torch.zeros((Np, Kp), dtype=F32, device=dy2.device)
     tb = torch.zeros((Np,), dtype=F32, device=dy2.device) if gb is not None else None
-    K.gemm_tn(dyp.contiguous(), xp.contiguous(), tw, tb)
+    K.gemm_tn(dyp.contiguous(), xp.contiguous(), tw, tb, splitm=1 if ordered else 0)
     gw.add_(tw[: gw.shape[0], : gw.shape[1]])
     if gb is not None:
         gb.add_(tb[: gb.numel()])
@@ -654,6 +707,7 @@ class LinearFn(torch.autograd.Function):
             out = _fwd_gemm(x2, weight, bias, rows, out_dtype=out_dtype)
         ctx.save_for_backward(x2, weight, bias)
         ctx.rows, ctx.has_res, ctx.xshape, ctx.xdtype = rows, residual is not None, x.shape, x.dtype
+        ctx.ordered = _ORDERED
         return out.reshape(*x.shape[:-1], N)
 
     @staticmethod
@@ -666,7 +720,7 @@ class LinearFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _dgrad_gemm(dy2, weight, ctx.rows, out_dtype=ctx.xdtype).reshape(ctx.xshape)
-        _wgrad(dy2, x2, weight, bias, ctx.rows)
+        _wgrad(dy2, x2, weight, bias, ctx.rows, ctx.ordered)
         return dx, None, None, (dy if ctx.has_res else None), None, None
 
 
@@ -1575,6 +1629,7 @@ class Conv3x3Fn(torch.autograd.Function):
         ctx.save_for_backward(col, weight, bias)
         ctx.shape = (B, H, W, C)
         ctx.in_dtype = x.dtype
+        ctx.ordered = _ORDERED
         return out.view(B, H * W, weight.shape[0])
 
     @staticmethod
@@ -1589,7 +1644,7 @@ class Conv3x3Fn(torch.autograd.Function):
             dx = dx if dx.dtype == ctx.in_dtype else dx.to(ctx.in_dtype)
         if weight.requires_grad:
             # (a biased conv takes the plain TN GEMM, whose epilogue also forms the column sums of dy = the bias gradient)
-            _conv_wgrad(dy2, col, weight, bias, Conv3x3Fn._wgrad_gemm if bias is None else None)
+            _conv_wgrad(dy2, col, weight, bias, _tn_ordered if ctx.ordered else (Conv3x3Fn._wgrad_gemm if bias is None else None))
         return dx, None, None
 
 
@@ -1818,6 +1873,7 @@ class ConvS2Fn(torch.autograd.Function):
         ctx.save_for_backward(col, weight, bias)
         ctx.shape = (B, H, W, C, Ho, Wo, Kp, Np)
         ctx.in_dtype = x.dtype
+        ctx.ordered = _ORDERED
         return out[:, :Co].reshape(B, Ho, Wo, Co) if Np != Co else out.view(B, Ho, Wo, Co)
 
     @staticmethod
@@ -1842,7 +1898,7 @@ class ConvS2Fn(torch.autograd.Function):
                     dxp[:, dyy:dyy + 2 * Ho:2, dxx:dxx + 2 * Wo:2, :] += dcol[..., t * C:(t + 1) * C]
                 dx = dxp[:, 1:1 + H, 1:1 + W, :].to(ctx.in_dtype)
         if weight.requires_grad:
-            _conv_wgrad(dy2, col, weight, bias)
+            _conv_wgrad(dy2, col, weight, bias, _tn_ordered if ctx.ordered else None)
         return dx, None, None
 
 
@@ -2142,3 +2198,74 @@ def conv_bn_act(x, weight, bn, *, kind, stride=1, residual=None, relu=False, tra
         raise ValueError(f"ResNet convolutions need channel counts that are multiples of 8, got weight {tuple(weight.shape)}")
     return ConvBnActFn.apply(x, residual, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, getattr(bn, "num_batches_tracked", None),
                              kind, stride, relu, train, bn.eps, getattr(bn, "momentum", 0.1), out_dtype)
+
+
+# --------------------------------------------------------------------------------------------
+# TransDSSL depth decoder in training: the non-GEMM passes (csrc/depth_head.hip)
+# --------------------------------------------------------------------------------------------
+class Upsample2xAcFn(torch.autograd.Function):
+    """x (B, H, W, C) -> (B, 2H, 2W, C): F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) on a channels-last map.
+    The backward is a gather (ATen's is an atomic scatter): two calls give the same bits."""
+
+    @staticmethod
+    def forward(ctx, x, out_dtype):
+        ctx.in_dtype = x.dtype
+        return K.upsample2x_ac_fwd(x if x.is_contiguous() else x.contiguous(), out_dtype=K._odt(out_dtype or x.dtype))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return K.upsample2x_ac_bwd(dy if dy.is_contiguous() else dy.contiguous(), out_dtype=ctx.in_dtype), None
+
+
+def upsample2x_ac(x_nhwc, *, out_dtype=None):
+    """out_dtype None: the input's dtype."""
+    return Upsample2xAcFn.apply(x_nhwc, out_dtype)
+
+
+class SoftmaxGateFn(torch.autograd.Function):
+    """The attention gate of a TransDSSL fusion block (reference pixel_decoder/transdssl.py FeatureFusionBlock_custom): res = a + b,
+    g = res * softmax_c(z) -> (res, g), fp32.  The attention is not stored: the backward recomputes it from z and takes the gradient of
+    g together with the one arriving at res (the block adds res again behind resConfUnit2) in one pass."""
+
+    @staticmethod
+    def forward(ctx, a, b, z):
+        c = lambda t: t if t.is_contiguous() else t.contiguous()
+        z = c(z)
+        res, g = K.softmax_gate_fwd(c(a), c(b), z, out_dtype=F32)
+        ctx.save_for_backward(z, res)
+        ctx.set_materialize_grads(False)
+        return res, g
+
+    @staticmethod
+    def backward(ctx, d_res_in, dg):
+        z, res = ctx.saved_tensors
+        c = lambda t: t if t is None or t.is_contiguous() else t.contiguous()
+        if dg is None:                                                   # g unused: res is a plain sum
+            return d_res_in, d_res_in, None
+        d_res, d_z = K.softmax_gate_bwd(c(dg), c(d_res_in), z, res, out_dtype=F32)
+        return d_res, d_res, d_z
+
+
+def softmax_gate(a, b, z):
+    return SoftmaxGateFn.apply(a, b, z)
+
+
+class SoftAttDepthFn(torch.autograd.Function):
+    """SoftAttDepth (reference pixel_decoder/transdssl.py:187-222): z (..., D) bin logits, grid (D) fp32 -> disp (...) fp32, the
+    expectation of the depth grid under softmax(z).  Saved: z alone."""
+
+    @staticmethod
+    def forward(ctx, z, grid):
+        z = z if z.is_contiguous() else z.contiguous()
+        ctx.save_for_backward(z, grid)
+        return K.soft_att_depth_fwd(z, grid)
+
+    @staticmethod
+    def backward(ctx, ddisp):
+        z, grid = ctx.saved_tensors
+        dd = ddisp.float()
+        return K.soft_att_depth_bwd(dd if dd.is_contiguous() else dd.contiguous(), z, grid, out_dtype=z.dtype), None
+
+
+def soft_att_depth(z, grid):
+    return SoftAttDepthFn.apply(z, grid)
