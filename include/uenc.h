@@ -666,6 +666,34 @@ int uenc_targets_write(const int* pan, const int* sizes, const int* seg_ids, con
                        const int* plane0, const int* T, long long ignore_label, unsigned char* masks, long long* sem_seg, int B, int H, int W,
                        int total_planes, uenc_stream_t stream);
 
+/* ---- evaluation statistics on the device (csrc/evalstats.hip; uenc.evaluation SemSegEvaluator / PanopticEvaluator) ----------------------------
+ * The same padded batch as the targets kernels: maps (B, H, W) int32, sizes (B, 2) = each image's own (h, w), pixels outside it are never
+ * counted; B <= 65535, H * W < 2^31 - 4096; all pointers DEVICE memory, naturally aligned (16-byte loads are used when H * W % 4 == 0 and
+ * the maps are 16-byte aligned).  Integer atomics only: the same input gives the same bits.  max_blocks: workgroups per image, 0 = as many
+ * as the image has chunks of 4096 pixels (at most 512); fewer make a workgroup take several chunks. */
+#define UENC_EVAL_MAX_CLASSES 1024
+#define UENC_EVAL_PQ_DIM 258 /* UENC_TARGETS_MAX_SEGMENTS + 2 */
+/* conf ((N + 1) x (N + 1)) int64, N = num_classes <= 1024: conf[p, g] += 1 per pixel.  C >= 1: pred is the scores (B, C, H, W) fp32 and
+ * p the argmax over the C planes (lowest index on a tie; the first NaN wins as in torch.argmax); C == 0: pred is a label map (B, H, W)
+ * int32.  p outside [0, N) counts in row N; g equal to ignore_label or outside [0, N) counts in column N. */
+int uenc_eval_confusion(const void* pred, const int* gt, const int* sizes, long long* conf, int B, int C, int H, int W, int num_classes,
+                        int ignore_label, int max_blocks, uenc_stream_t stream);
+/* inter (B, 258, 258) int32, ZERO-FILLED by the caller: inter[b, r, c] += 1 per pixel, r from the pixel's ground-truth id and c from its
+ * predicted id: 0 for id 0 (VOID), 1 + the id's row of gt_ids / pred_ids (B, 256; n_gt / n_pred (B) in use, rules as for seg_ids above),
+ * n + 1 for an id that has no row ("unknown").  Rows above n_gt + 1 and columns above n_pred + 1 stay zero. */
+int uenc_eval_pq_intersect(const int* pred, const int* gt, const int* sizes, const int* gt_ids, const int* n_gt, const int* pred_ids,
+                           const int* n_pred, int* inter, int B, int H, int W, int max_blocks, uenc_stream_t stream);
+/* panopticapi's pq_compute_single_core on inter, one workgroup per image; gt_cat, gt_crowd, pred_cat (B, 256) int32, K categories <= 1024.
+ * Areas are the row / column sums.  A pair of real segments with inter > 0, the same category and a non-crowd ground truth matches when
+ * 2 * inter > union = area_pred + area_gt - inter - inter[VOID, pred].  Every byte of the outputs is written:
+ *   rec (B, 256, 4)  per ground-truth row: matched row of pred_ids or -1, inter, union (0, 0 without a match), category (-1 above n_gt)
+ *   fn (B, K)        unmatched non-crowd ground-truth rows with area > 0, per category
+ *   fp (B, K)        unmatched predicted rows unless 2 * (inter[VOID, pred] + their pixels over crowds of their category) > area_pred
+ *   unknown (B)      pixels whose predicted id has no row
+ * A category outside [0, K) is counted nowhere. */
+int uenc_eval_pq_match(const int* inter, const int* n_gt, const int* n_pred, const int* gt_cat, const int* gt_crowd, const int* pred_cat,
+                       int* rec, int* fp, int* fn, int* unknown, int B, int K, uenc_stream_t stream);
+
 /* ---- depth decoder in training: the non-GEMM passes of TransDSSL (csrc/depth_head.hip) ----------------------------------------------------
  * Channels-last maps, operands fp32 | bf16 by their dtype tag, arithmetic in fp32, every pointer 16-byte aligned.  No float atomics:
  * each backward is a gather in a fixed order, two calls give the same bits. */

@@ -151,6 +151,10 @@ _SIGNATURES = {
     # training targets from a panoptic id map (csrc/targets.hip)
     "uenc_targets_area": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "uenc_targets_write": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    # evaluation statistics: confusion matrix, panoptic intersection matrix and matching (csrc/evalstats.hip)
+    "uenc_eval_confusion": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "uenc_eval_pq_intersect": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "uenc_eval_pq_match": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
     # depth decoder in training: x2 align-corners upsample, softmax gate, soft-attention depth head (csrc/depth_head.hip)
     "uenc_upsample2x_ac_fwd": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
     "uenc_upsample2x_ac_bwd": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p],

@@ -5,10 +5,29 @@ upstream).  Evaluators: `SemSegEvaluator` (confusion-matrix mIoU / pixel accurac
 them [not in reference]) and the two depth evaluators of the "sequence" branch, whose arithmetic is plain numpy in the reference:
 `KITTIDepthEvaluator` (kitti_evaluation.py:71-279: velodyne ground truth, Eigen crop, median scaling, the seven depth metrics of
 `compute_errors` :282-299) and `CityscapesDepthEvaluator` (cityscapes_evaluation.py:231-362).  The reference's Cityscapes instance /
-semantic and COCO evaluators wrap third-party scorers (cityscapesscripts, pycocotools, panopticapi) that are not installable here: their
+semantic and COCO instance evaluators wrap third-party scorers (cityscapesscripts, pycocotools) that are not installable here: their
 names resolve and raise when constructed.  `inference_on_dataset`, `compute_errors`, the KITTI depth-map projection and the KITTI
 evaluation are pinned by fixtures generated from the reference's own functions (oracle/make_data_eval_golden.py ->
 tests/golden/data_eval.npz, tests/test_data_eval_cpu.py).
+
+The two segmentation evaluators of the reference's driver (train_net.py:94-108) score here without a third-party package and, with
+accumulate="device", without leaving the GPU until `evaluate()` (csrc/evalstats.hip): `SemSegEvaluator` and `PanopticEvaluator` /
+`COCOPanopticEvaluator`; `build_evaluator` picks them as the reference's Trainer does.  Everything they count is an integer, so the
+host and the device paths agree exactly.
+
+Panoptic quality: the rules of panopticapi's `pq_compute_single_core` and `PQStat.pq_average`, which `pq_match_host`,
+uenc_eval_pq_match and `PanopticEvaluator.evaluate` implement literally.  Per image, inter[g, p] = the pixels that have ground-truth id g
+and predicted id p; id 0 is VOID on both sides; an id that its side's segments_info does not list is "unknown", kept apart from VOID.
+  * Areas are row and column sums of inter: a predicted segment's area includes its pixels over VOID and over unknown ground truth.
+  * Candidate pairs have inter > 0 with a listed segment on both sides.  A pair is skipped if the ground truth is a crowd, and if the
+    categories differ.  union = area_pred + area_gt - inter - inter[VOID, pred]; if inter / union > 0.5 (decided as 2 inter > union)
+    the pair is a TP of its category, both segments are matched and the IoU is added.  Such a match is unique.
+  * FN: every unmatched, non-crowd listed ground-truth segment with area > 0 adds to fn[category].
+  * FP: for every unmatched predicted segment, v = inter[VOID, pred] + the sum of inter[g, pred] over crowds g of its category; it is
+    skipped if v / area_pred > 0.5 (strictly), else it adds to fp[category].
+  * Per category with tp + fp + fn > 0: PQ = iou / (tp + fp / 2 + fn / 2), SQ = iou / tp (0 when tp == 0), RQ = tp / (tp + fp / 2 +
+    fn / 2); All / Things / Stuff are the means over the categories counted; with none counted the result is 0.
+  * Pixels of an unknown predicted id are an error (panopticapi raises as well): `evaluate()` raises.
 """
 import datetime
 import logging
@@ -139,19 +158,71 @@ def inference_on_dataset(model, data_loader, evaluator: Union[DatasetEvaluator, 
     return {} if results is None else results
 
 
+def _check_accumulate(accumulate: str) -> str:
+    if accumulate not in ("host", "device"):
+        raise ValueError(f'accumulate must be "host" or "device", got {accumulate!r}')
+    return accumulate
+
+
+def _device_map(a, device, what: str) -> torch.Tensor:
+    """An (H, W) integer map as a contiguous int32 tensor on `device`: an upload for host data, no copy for a device int32 tensor."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.int32))
+    if t.dim() != 2:
+        raise ValueError(f"{what} must be an (H, W) map, got {tuple(t.shape)}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _need_device(t, what: str):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError(f'accumulate="device" counts on the GPU where the model left {what}: it must be a GPU tensor '
+                         f'(got {"a " + str(t.device) + " tensor" if torch.is_tensor(t) else type(t).__name__}); use accumulate="host" for host data')
+
+
+class _SizeCache(dict):
+    """(H, W, device) -> the (1, 2) int32 size row the kernels take, uploaded once per size."""
+
+    def __missing__(self, key):
+        h, w, device = key
+        self[key] = torch.tensor([[h, w]], dtype=torch.int32).to(device)
+        return self[key]
+
+
 class SemSegEvaluator(DatasetEvaluator):
     """mIoU / fwIoU / mACC / pACC of the "sem_seg" outputs against "sem_seg" ground-truth maps held by the dataset dicts (key
     `gt_key`, an (H, W) integer array or tensor), accumulated as an (N+1) x (N+1) confusion matrix like
-    detectron2.evaluation.SemSegEvaluator; single process (the sharded multi-rank gather is Detectron2 plumbing)."""
+    detectron2.evaluation.SemSegEvaluator; single process (the sharded multi-rank gather is Detectron2 plumbing).
+    accumulate="host": argmax on the device, the label map copied to the host and counted with numpy.  accumulate="device": the class
+    argmax and the counting happen in uenc_eval_confusion on the (C, H, W) scores where they are; `process` uploads the ground truth
+    (or takes a device tensor), copies nothing back and does not synchronise; the matrix is read once, in `evaluate`."""
 
-    def __init__(self, num_classes: int, ignore_label: int = 255, gt_key: str = "sem_seg_gt"):
+    def __init__(self, num_classes: int, ignore_label: int = 255, gt_key: str = "sem_seg_gt", accumulate: str = "host"):
         self._num_classes, self._ignore_label, self._gt_key = num_classes, ignore_label, gt_key
+        self._accumulate = _check_accumulate(accumulate)
+        self._sizes = _SizeCache()
         self.reset()
 
     def reset(self):
         self._conf = np.zeros((self._num_classes + 1, self._num_classes + 1), dtype=np.int64)
+        self._dev_conf = None                         # allocated on the device of the first prediction
+
+    def _process_device(self, inputs, outputs):
+        from . import kernels as K
+        for inp, out in zip(inputs, outputs):
+            scores = out["sem_seg"]
+            _need_device(scores, 'out["sem_seg"]')
+            if scores.dim() != 3:
+                raise ValueError(f'out["sem_seg"] must be (C, H, W), got {tuple(scores.shape)}')
+            gt = _device_map(inp[self._gt_key], scores.device, self._gt_key)
+            if tuple(gt.shape) != tuple(scores.shape[1:]):
+                raise ValueError(f"prediction {tuple(scores.shape[1:])} and ground truth {tuple(gt.shape)} differ in size")
+            if self._dev_conf is None:
+                self._dev_conf = torch.zeros(self._conf.shape, dtype=torch.int64, device=scores.device)
+            H, W = gt.shape
+            K.eval_confusion(scores.float().contiguous()[None], gt[None], self._sizes[(H, W, scores.device)], self._dev_conf, self._ignore_label)
 
     def process(self, inputs, outputs):
+        if self._accumulate == "device":
+            return self._process_device(inputs, outputs)
         for inp, out in zip(inputs, outputs):
             pred = out["sem_seg"].argmax(dim=0).to("cpu").numpy().astype(np.int64)
             gt = np.asarray(inp[self._gt_key]).astype(np.int64)
@@ -161,6 +232,9 @@ class SemSegEvaluator(DatasetEvaluator):
 
     def evaluate(self):
         N = self._num_classes
+        if self._dev_conf is not None:                # the one read-back
+            self._conf = self._conf + self._dev_conf.cpu().numpy()
+            self._dev_conf = None
         tp = self._conf.diagonal()[:-1].astype(np.float64)
         pos_gt = np.sum(self._conf[:-1, :-1], axis=0).astype(np.float64)
         pos_pred = np.sum(self._conf[:-1, :-1], axis=1).astype(np.float64)
@@ -173,6 +247,211 @@ class SemSegEvaluator(DatasetEvaluator):
         res = {"mIoU": 100 * float(np.nansum(iou) / max(np.sum(iou_valid), 1)), "fwIoU": 100 * float(np.nansum(iou * class_weights)),
                "mACC": 100 * float(np.nansum(acc) / max(np.sum(acc_valid), 1)), "pACC": 100 * float(np.sum(tp) / max(np.sum(pos_gt), 1.0))}
         return OrderedDict({"sem_seg": res})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# panoptic quality (the rules are stated in the module docstring)
+# ---------------------------------------------------------------------------------------------------------------------
+PQ_MAX_SEGMENTS = 256          # per image and side on the device path: the rows of the kernels' id table
+
+
+def rgb2id(color):
+    """panopticapi.utils.rgb2id: an (H, W, 3) uint8 panoptic PNG -> the (H, W) id map R + 256 G + 65536 B (or one colour -> one id)."""
+    color = np.asarray(color)
+    if color.ndim == 3:
+        color = color.astype(np.int32)
+        return color[:, :, 0] + 256 * color[:, :, 1] + 256 * 256 * color[:, :, 2]
+    return int(color[0]) + 256 * int(color[1]) + 256 * 256 * int(color[2])
+
+
+def pq_intersect_host(pred: np.ndarray, gt: np.ndarray, gt_ids, pred_ids) -> np.ndarray:
+    """inter (n_gt + 2, n_pred + 2) int64 of two (H, W) id maps: row / column 0 = id 0 (VOID), 1 + k = the k-th listed id (of two equal
+    ids the first; an id <= 0 lists nothing), n + 1 = an id that is not listed.  What uenc_eval_pq_intersect counts, with numpy."""
+    def rows(m, ids):
+        first = {}
+        for k, i in enumerate(ids):
+            if i > 0:
+                first.setdefault(int(i), k + 1)
+        values, inverse = np.unique(m, return_inverse=True)
+        row = np.array([0 if v == 0 else first.get(int(v), len(ids) + 1) for v in values], dtype=np.int64)
+        return row[inverse.reshape(-1)]
+    if pred.shape != gt.shape:
+        raise ValueError(f"prediction {pred.shape} and ground truth {gt.shape} differ in size")
+    R, C = len(gt_ids) + 2, len(pred_ids) + 2
+    return np.bincount(rows(gt, gt_ids) * C + rows(pred, pred_ids), minlength=R * C).reshape(R, C)
+
+
+def pq_match_host(inter: np.ndarray, gt_cat, gt_crowd, pred_cat, num_categories: int):
+    """The matching rules on one image's intersection matrix -> rec (n_gt, 4) int64 = matched predicted row or -1, inter, union, category
+    per ground-truth row; fp (K), fn (K) int64; the pixel count of unlisted predicted ids.  What uenc_eval_pq_match computes."""
+    ng, npd = len(gt_cat), len(pred_cat)
+    area_g, area_p = inter.sum(axis=1), inter.sum(axis=0)
+    rec = np.zeros((ng, 4), dtype=np.int64)
+    rec[:, 0], rec[:, 3] = -1, gt_cat
+    fp, fn = np.zeros(num_categories, dtype=np.int64), np.zeros(num_categories, dtype=np.int64)
+    hit, crowd = np.zeros(npd, dtype=bool), np.zeros(npd, dtype=np.int64)
+    for g, p in zip(*np.nonzero(inter[1:ng + 1, 1:npd + 1])):
+        v = int(inter[g + 1, p + 1])
+        if gt_cat[g] != pred_cat[p]:
+            continue
+        if gt_crowd[g]:
+            crowd[p] += v
+            continue
+        union = int(area_p[p + 1]) + int(area_g[g + 1]) - v - int(inter[0, p + 1])
+        if 2 * v > union:                                               # IoU > 0.5, exactly
+            rec[g, :3] = (p, v, union)
+            hit[p] = True
+    for g in range(ng):
+        if rec[g, 0] < 0 and not gt_crowd[g] and area_g[g + 1] > 0:
+            fn[gt_cat[g]] += 1
+    for p in range(npd):
+        if not hit[p] and not 2 * (int(inter[0, p + 1]) + int(crowd[p])) > int(area_p[p + 1]):
+            fp[pred_cat[p]] += 1
+    return rec, fp, fn, int(area_p[npd + 1])
+
+
+class PanopticEvaluator(DatasetEvaluator):
+    """PQ / SQ / RQ (all, things, stuff) of the "panoptic_seg" outputs = (id map, segments_info), as `panoptic_inference_fused` returns
+    them, against the dataset dicts' panoptic annotation: `dict[gt_key]`, an (H, W) id map, with `dict["segments_info"]` (id, category_id,
+    iscrowd: the keys the training forward reads), else `pan_seg_file_name`, a panoptic PNG.  Category ids on both sides are the
+    contiguous ones, 0 <= id < num_categories; `thing_ids` splits them into things and stuff.
+    accumulate="host": numpy, any number of segments.  accumulate="device": uenc_eval_pq_intersect + uenc_eval_pq_match on the maps where
+    they are (the ground truth is uploaded, or taken as a device tensor), at most 256 segments per image and side; `process` copies
+    nothing back, the per-image records stay on the device until `evaluate` gathers them in one copy.  Both paths sum the IoUs of the
+    matched pairs with the same host code, in float64, in image order then row order: they return equal floats."""
+
+    def __init__(self, thing_ids, num_categories: int, accumulate: str = "host", gt_key: str = "pan_seg"):
+        self._things = sorted({int(t) for t in thing_ids})
+        self._K, self._gt_key = int(num_categories), gt_key
+        self._accumulate = _check_accumulate(accumulate)
+        if not self._K >= 1 or any(not 0 <= t < self._K for t in self._things):
+            raise ValueError(f"thing_ids {self._things} must lie in [0, num_categories = {num_categories})")
+        self._logger = logging.getLogger(__name__)
+        self.reset()
+
+    def reset(self):
+        self._records = []            # host: (rec, fp, fn, unknown) per image; device: (the match kernel's buffer, n_gt)
+
+    def _ground_truth(self, inp):
+        if self._gt_key in inp:
+            pan = inp[self._gt_key]
+        elif "pan_seg_file_name" in inp:
+            from PIL import Image
+            with Image.open(inp["pan_seg_file_name"]) as im:
+                pan = rgb2id(np.asarray(im.convert("RGB")))
+        else:
+            raise KeyError(f'a dataset dict needs "{self._gt_key}" (an id map) or "pan_seg_file_name" for the panoptic evaluation')
+        return pan, [(int(s["id"]), self._category(s), int(s.get("iscrowd", 0))) for s in inp["segments_info"]]
+
+    def _category(self, seg) -> int:
+        c = int(seg["category_id"])
+        if not 0 <= c < self._K:
+            raise ValueError(f"segment {seg.get('id')} has category {c}, outside [0, {self._K})")
+        return c
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            pred, info = out["panoptic_seg"]
+            pan, gt_segs = self._ground_truth(inp)
+            pred_segs = [(int(s["id"]), self._category(s)) for s in info]
+            if self._accumulate == "device":
+                self._records.append(self._process_device(pred, pred_segs, pan, gt_segs))
+                continue
+            pred = pred.cpu().numpy() if torch.is_tensor(pred) else np.asarray(pred)
+            pan = pan.cpu().numpy() if torch.is_tensor(pan) else np.asarray(pan)
+            inter = pq_intersect_host(pred, pan, [i for i, _, _ in gt_segs], [i for i, _ in pred_segs])
+            self._records.append(pq_match_host(inter, [c for _, c, _ in gt_segs], [k for _, _, k in gt_segs], [c for _, c in pred_segs], self._K))
+
+    def _process_device(self, pred, pred_segs, pan, gt_segs):
+        from . import kernels as K
+        _need_device(pred, 'the id map of out["panoptic_seg"]')
+        S, ng, npd = PQ_MAX_SEGMENTS, len(gt_segs), len(pred_segs)
+        if ng > S or npd > S:
+            raise ValueError(f'accumulate="device" takes at most {S} segments per image on either side (the kernels\' id table); this image has '
+                             f'{ng} ground-truth and {npd} predicted segments: use accumulate="host"')
+        pred = _device_map(pred, pred.device, "the predicted id map")
+        gt = _device_map(pan, pred.device, "the ground-truth id map")
+        if gt.shape != pred.shape:
+            raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
+        table = np.zeros(5 * S + 4, dtype=np.int32)                       # K._eval_pq_table with B = 1: one upload
+        if ng:
+            table[0:ng], table[2 * S:2 * S + ng], table[3 * S:3 * S + ng] = np.asarray(gt_segs, dtype=np.int64).T
+        if npd:
+            table[S:S + npd], table[4 * S:4 * S + npd] = np.asarray(pred_segs, dtype=np.int64).T
+        table[5 * S:] = (ng, npd) + tuple(gt.shape)
+        table = torch.from_numpy(table).to(pred.device)
+        inter = K.eval_pq_intersect(pred[None], gt[None], table)
+        return K.eval_pq_match(inter, table, self._K), ng
+
+    def _gathered(self):
+        """Every image's (rec (n_gt, 4), fp, fn, unknown) as int64 numpy, in image order: for the device path its one device-to-host copy."""
+        records = self._records
+        if self._accumulate == "device" and records:
+            from . import kernels as K
+            host = torch.stack([r for r, _ in records]).cpu().numpy().astype(np.int64)
+            records = []
+            for row, (_, ng) in zip(host, self._records):
+                rec, fp, fn, unknown = K.eval_pq_unpack(row, 1, self._K)
+                records.append((rec[0, :ng], fp[0], fn[0], int(unknown[0])))
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            box = [None] * dist.get_world_size()
+            dist.all_gather_object(box, records)
+            records = [r for part in box for r in part]
+        return records
+
+    def evaluate(self):
+        records = self._gathered()
+        if not _is_main_process():
+            return None
+        K = self._K
+        unknown = [(i, r[3]) for i, r in enumerate(records) if r[3]]
+        if unknown:
+            raise ValueError(f"{len(unknown)} image(s) have pixels of a predicted id that their segments_info does not list "
+                             f"(first: image {unknown[0][0]}, {unknown[0][1]} pixels)")
+        iou, tp = np.zeros(K, dtype=np.float64), np.zeros(K, dtype=np.int64)
+        fp, fn = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        for rec, img_fp, img_fn, _ in records:
+            for col, inter, union, cat in rec.tolist():
+                if col >= 0:
+                    tp[cat] += 1
+                    iou[cat] += inter / union
+            fp += img_fp
+            fn += img_fn
+        res = {}
+        for name, cats in (("", range(K)), ("_th", self._things), ("_st", [c for c in range(K) if c not in set(self._things)])):
+            pq = sq = rq = 0.0
+            n = 0
+            for c in cats:
+                t, p, f = int(tp[c]), int(fp[c]), int(fn[c])
+                if t + p + f == 0:
+                    continue                                              # a category never seen is not part of the mean
+                n += 1
+                pq += float(iou[c]) / (t + 0.5 * p + 0.5 * f)
+                sq += float(iou[c]) / t if t else 0.0
+                rq += t / (t + 0.5 * p + 0.5 * f)
+            for key, v in (("PQ", pq), ("SQ", sq), ("RQ", rq)):
+                res[key + name] = 100 * v / n if n else 0.0
+        self._stats = {"tp": tp, "fp": fp, "fn": fn, "iou": iou}
+        return OrderedDict({"panoptic_seg": res})
+
+
+class COCOPanopticEvaluator(PanopticEvaluator):
+    """detectron2.evaluation.COCOPanopticEvaluator's place in the reference's train_net.py:100-108, scored by `PanopticEvaluator` instead
+    of panopticapi: thing ids and the number of categories come from the dataset's metadata (the contiguous train ids that
+    `thing_dataset_id_to_contiguous_id` / `stuff_dataset_id_to_contiguous_id` map to, as uenc.datasets registers them and as
+    the dataset dicts and the predictions carry them).  Nothing is written to `output_dir`."""
+
+    def __init__(self, dataset_name: str, output_dir: Optional[str] = None, accumulate: str = "host", gt_key: str = "pan_seg"):
+        from .data import MetadataCatalog
+        meta = MetadataCatalog.get(dataset_name)
+        things = getattr(meta, "thing_dataset_id_to_contiguous_id", None)
+        stuff = getattr(meta, "stuff_dataset_id_to_contiguous_id", None)
+        if things is None or stuff is None:
+            raise ValueError(f"dataset {dataset_name!r} has no thing / stuff_dataset_id_to_contiguous_id metadata: is it a registered panoptic dataset?")
+        cats = set(things.values()) | set(stuff.values())
+        self._dataset_name, self._output_dir = dataset_name, output_dir
+        super().__init__(sorted(set(things.values())), max(cats) + 1, accumulate=accumulate, gt_key=gt_key)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -371,3 +650,38 @@ COCOEvaluator = _needs("COCOEvaluator", "pycocotools")
 InstanceSegEvaluator = _needs("InstanceSegEvaluator", "pycocotools")
 CityscapesInstanceEvaluator = _needs("CityscapesInstanceEvaluator", "cityscapesscripts")
 CityscapesSemSegEvaluator = _needs("CityscapesSemSegEvaluator", "cityscapesscripts")
+
+
+def build_evaluator(cfg, dataset_name: str, accumulate: str = "device", output_folder: Optional[str] = None):
+    """The reference's Trainer.build_evaluator (train_net.py:75-149): the evaluator(s) for a dataset by its metadata's `evaluator_type`
+    and cfg.MODEL.TEST.  The segmentation evaluators count on the device by default.  The branches whose scorers are third-party packages
+    (Cityscapes instance / semantic scripts, COCO instance AP) construct the names that raise."""
+    from .data import MetadataCatalog
+    meta = MetadataCatalog.get(dataset_name)
+    evaluator_type = getattr(meta, "evaluator_type", None)
+    if output_folder is None:
+        output_folder = os.path.join(cfg.OUTPUT_DIR, "inference")
+    test = cfg.MODEL.TEST
+    evaluators = []
+    if evaluator_type == "kitti_depth" and test.DEPTH_ON:
+        evaluators.append(KITTIDepthEvaluator(dataset_name))
+    if evaluator_type in ("sem_seg", "ade20k_panoptic_seg"):
+        evaluators.append(SemSegEvaluator(len(meta.stuff_classes), ignore_label=getattr(meta, "ignore_label", 255), accumulate=accumulate))
+    if evaluator_type in ("coco_panoptic_seg", "ade20k_panoptic_seg", "cityscapes_panoptic_seg", "mapillary_vistas_panoptic_seg") and test.PANOPTIC_ON:
+        evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder, accumulate=accumulate))
+    if evaluator_type == "cityscapes_instance":
+        return CityscapesInstanceEvaluator(dataset_name)
+    if evaluator_type == "cityscapes_sem_seg":
+        return CityscapesSemSegEvaluator(dataset_name)
+    if evaluator_type == "cityscapes_panoptic_seg":
+        if test.SEMANTIC_ON:
+            evaluators.append(CityscapesSemSegEvaluator(dataset_name))
+        if test.INSTANCE_ON:
+            evaluators.append(CityscapesInstanceEvaluator(dataset_name))
+    if evaluator_type == "cityscapes_depth" and test.DEPTH_ON:
+        evaluators.append(CityscapesDepthEvaluator(dataset_name))
+    if evaluator_type == "ade20k_panoptic_seg" and test.INSTANCE_ON:
+        evaluators.append(InstanceSegEvaluator(dataset_name, output_dir=output_folder))
+    if not evaluators:
+        raise NotImplementedError("no Evaluator for the dataset {} with the type {}".format(dataset_name, evaluator_type))
+    return evaluators[0] if len(evaluators) == 1 else DatasetEvaluators(evaluators)

@@ -1255,6 +1255,80 @@ def targets_write(pan: torch.Tensor, table: torch.Tensor, plan: torch.Tensor, to
     return masks, sem
 
 
+# ---- evaluation statistics on the device (csrc/evalstats.hip) ------------------------------------------------------------------------------------
+EVAL_MAX_CLASSES = 1024
+EVAL_PQ_DIM = TARGETS_MAX_SEGMENTS + 2          # VOID, 256 table rows, "unknown"
+
+
+def eval_confusion(pred: torch.Tensor, gt: torch.Tensor, sizes: torch.Tensor, conf: torch.Tensor, ignore_label: int, max_blocks: int = 0):
+    """conf ((N + 1), (N + 1)) int64 += the confusion counts conf[pred, gt] of one padded batch.  pred: scores (B, C, H, W) fp32 (the class
+    argmax is taken in the kernel) or a label map (B, H, W) int32; gt (B, H, W) int32; sizes (B, 2) int32 = each image's own (h, w).
+    Nothing is copied back.  uenc_eval_confusion."""
+    _dev(gt, "gt", torch.int32, 3); _dev(sizes, "sizes", torch.int32, 2); _dev(conf, "conf", torch.int64, 2)
+    B, H, W = gt.shape
+    if pred.dim() == 4:
+        _dev(pred, "pred", torch.float32, 4)
+        C = int(pred.shape[1])
+        ok = C >= 1 and tuple(pred.shape) == (B, C, H, W)
+    else:
+        _dev(pred, "pred", torch.int32, 3)
+        C, ok = 0, tuple(pred.shape) == (B, H, W)
+    N = int(conf.shape[0]) - 1
+    if not ok or tuple(sizes.shape) != (B, 2) or conf.shape[0] != conf.shape[1]:
+        raise capi.UencError(f"eval_confusion: pred {tuple(pred.shape)}, gt {tuple(gt.shape)}, sizes {tuple(sizes.shape)}, conf {tuple(conf.shape)} do not fit")
+    check(lib.uenc_eval_confusion(pred.data_ptr(), gt.data_ptr(), sizes.data_ptr(), conf.data_ptr(), B, C, H, W, N, int(ignore_label),
+                                  int(max_blocks), stream_ptr()), "eval_confusion")
+    return conf
+
+
+def _eval_pq_table(table, B):
+    """The packed int32 table of a panoptic-quality call (one upload): gt_ids, pred_ids, gt_cat, gt_crowd, pred_cat (B, 256 each), n_gt (B),
+    n_pred (B), sizes (B, 2), in that order -> the eight views."""
+    S = TARGETS_MAX_SEGMENTS
+    _dev(table, "table", torch.int32, 1)
+    if table.numel() != B * (5 * S + 4):
+        raise capi.UencError(f"eval_pq: a table of B * {5 * S + 4} entries is expected")
+    cut = [B * S] * 5 + [B, B, 2 * B]
+    return torch.split(table, cut)
+
+
+def eval_pq_intersect(pred: torch.Tensor, gt: torch.Tensor, table: torch.Tensor, max_blocks: int = 0) -> torch.Tensor:
+    """-> inter (B, 258, 258) int32: pixels per (ground-truth row, predicted column); row / column 0 is id 0 (VOID), 1 + k the k-th id of
+    the table, n + 1 an id the table does not list.  pred, gt (B, H, W) int32; table as `_eval_pq_table`.  uenc_eval_pq_intersect."""
+    _dev(pred, "pred", torch.int32, 3); _dev(gt, "gt", torch.int32, 3)
+    B, H, W = gt.shape
+    if tuple(pred.shape) != (B, H, W):
+        raise capi.UencError(f"eval_pq_intersect: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ")
+    gt_ids, pred_ids, _, _, _, n_gt, n_pred, sizes = _eval_pq_table(table, B)
+    inter = torch.zeros((B, EVAL_PQ_DIM, EVAL_PQ_DIM), dtype=torch.int32, device=gt.device)
+    check(lib.uenc_eval_pq_intersect(pred.data_ptr(), gt.data_ptr(), sizes.data_ptr(), gt_ids.data_ptr(), n_gt.data_ptr(), pred_ids.data_ptr(),
+                                     n_pred.data_ptr(), inter.data_ptr(), B, H, W, int(max_blocks), stream_ptr()), "eval_pq_intersect")
+    return inter
+
+
+def eval_pq_match(inter: torch.Tensor, table: torch.Tensor, num_categories: int) -> torch.Tensor:
+    """-> one flat int32 buffer of B * (1024 + 2 K + 1) entries (one allocation; `eval_pq_unpack` gives its parts): rec (B, 256, 4) =
+    matched predicted row or -1, inter, union, category per ground-truth row; fp (B, K); fn (B, K); unknown (B) = the pixels of predicted
+    ids the table does not list.  uenc_eval_pq_match."""
+    _dev(inter, "inter", torch.int32, 3)
+    B, K = int(inter.shape[0]), int(num_categories)
+    if tuple(inter.shape[1:]) != (EVAL_PQ_DIM, EVAL_PQ_DIM) or not 1 <= K <= EVAL_MAX_CLASSES:
+        raise capi.UencError(f"eval_pq_match: inter (B, {EVAL_PQ_DIM}, {EVAL_PQ_DIM}) and 1 <= K <= {EVAL_MAX_CLASSES} are expected")
+    _, _, gt_cat, gt_crowd, pred_cat, n_gt, n_pred, _ = _eval_pq_table(table, B)
+    out = torch.empty(B * (4 * TARGETS_MAX_SEGMENTS + 2 * K + 1), dtype=torch.int32, device=inter.device)
+    rec, fp, fn, unknown = eval_pq_unpack(out, B, K)
+    check(lib.uenc_eval_pq_match(inter.data_ptr(), n_gt.data_ptr(), n_pred.data_ptr(), gt_cat.data_ptr(), gt_crowd.data_ptr(), pred_cat.data_ptr(),
+                                 rec.data_ptr(), fp.data_ptr(), fn.data_ptr(), unknown.data_ptr(), B, K, stream_ptr()), "eval_pq_match")
+    return out
+
+
+def eval_pq_unpack(out, B: int, num_categories: int):
+    """The buffer of `eval_pq_match` (a tensor or a numpy array) -> views rec (B, 256, 4), fp (B, K), fn (B, K), unknown (B)."""
+    S, K = TARGETS_MAX_SEGMENTS, int(num_categories)
+    a, b, c = B * 4 * S, B * (4 * S + K), B * (4 * S + 2 * K)
+    return out[:a].reshape(B, S, 4), out[a:b].reshape(B, K), out[b:c].reshape(B, K), out[c:]
+
+
 # ---- MonodepthLoss: view synthesis + photometric loss (csrc/monodepth.hip) -----------------------------------------------------------------
 # slots of the 67-pointer descriptor of uenc_view_synth_fwd / _bwd (struct VsDesc)
 _VS = {"disp": 0, "cflow": 4, "mask": 12, "T": 20, "K": 21, "invK": 22, "src": 23, "color": 24, "sample": 25, "sample_ego": 26, "sample_cmp": 27,
