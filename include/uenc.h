@@ -716,6 +716,39 @@ int uenc_soft_att_depth_fwd(const void* z, int z_dtype, const float* grid, float
 int uenc_soft_att_depth_bwd(const float* ddisp, const void* z, int z_dtype, const float* grid, void* dz, int dz_dtype, long P, int D,
                             uenc_stream_t stream);
 
+/* ---- training-time augmentation of one sample (csrc/augment.hip; uenc/train_data.py apply_plans) -------------------------------------------
+ * The plan is the host's: the source (in_h, in_w) is resized to (rs_h, rs_w), the window (x0, y0, cw, ch) of the resized image is kept,
+ * flipped horizontally when flip == 1, and padded (or cropped) at the right and bottom to (out_h, out_w).  Only the window is computed.
+ * All pointers are DEVICE memory; int tables 4-byte aligned; integers only except the HSV -> BGR stage (float32, single rounded
+ * operations: the same bits as the host's numpy expression).  No atomics, nothing is read back. */
+#define UENC_AUG_TILE_W 64
+#define UENC_AUG_TILE_H 16
+#define UENC_AUG_MAX_TAPS 7
+#define UENC_AUG_COLOUR_SAT 1            /* the saturation stage runs (HSV round trip, value table 2 on S) */
+#define UENC_AUG_COLOUR_HUE 2            /* the hue stage runs (HSV round trip, H = (H + hue) mod 180) */
+#define UENC_AUG_COLOUR_CONTRAST_FIRST 4 /* contrast before saturation and hue, else after them */
+#define UENC_AUG_COLOUR_RGB 8            /* the frames are RGB (else BGR) */
+#define UENC_AUG_COLOUR_TAB_INTS 704     /* 3 x 256 bytes of value tables (brightness, contrast, saturation), sdiv[256], hdiv[256] */
+/* 1 when a 64 x 16 output tile of this resize fits the kernel's LDS (<= 165 source pixels x 40 source rows, kx, ky <= 7 taps), else 0. */
+int uenc_augment_tile_fits(int in_h, int in_w, int rs_h, int rs_w, int kx, int ky);
+/* dst (F, 3, out_h, out_w) uint8, every byte written, from F frames (in_h, in_w, 3) uint8, frame_stride bytes apart: PIL's BILINEAR
+ * resize restricted to the window, then the SSD colour stages, flip, pad with pad_value.
+ * col_tab: for each of the cw window columns the first source column, the tap count (<= kx) and kx 22-bit fixed-point coefficients,
+ * laid out as first[cw], count[cw], coeff[cw][kx]; row_tab alike for the ch window rows with ky.  A pass computes
+ * clip(((1 << 21) + sum(pixel * coeff)) >> 22, 0, 255), the horizontal pass into a uint8 intermediate.
+ * colour_tab (UENC_AUG_COLOUR_TAB_INTS ints) may be NULL with colour_flags == 0: no colour stage.  hue in (-180, 180).
+ * -1: a null / misaligned pointer, an empty size, a window outside the resized image, or a plan whose tile does not fit (see above). */
+int uenc_augment_image(const unsigned char* src, long frame_stride, int F, int in_h, int in_w, int rs_h, int rs_w, int x0, int y0, int cw,
+                       int ch, const int* col_tab, int kx, const int* row_tab, int ky, const int* colour_tab, int colour_flags, int hue,
+                       int flip, int out_h, int out_w, int pad_value, unsigned char* dst, uenc_stream_t stream);
+/* pan_out (out_h, out_w) int32 = r + 256 g + 65536 b of the panoptic PNG pan (in_h, in_w, 3) uint8 at [pan_row[y], pan_col[x]], 0 in the
+ * padding; label_out (out_h, out_w) int32 = label[lab_row[y], lab_col[x]] (label_bytes 1: uint8, 4: int32), ignore_label in the padding.
+ * The tables hold SOURCE indices of the window's ch rows / cw columns (nearest resize; the two maps follow different libraries' rounding).
+ * label, lab_col, lab_row and label_out may all be NULL: no label map. */
+int uenc_augment_labels(const unsigned char* pan, const void* label, int label_bytes, int in_h, int in_w, int rs_h, int rs_w, int x0, int y0,
+                        int cw, int ch, const int* pan_col, const int* pan_row, const int* lab_col, const int* lab_row, int flip, int out_h,
+                        int out_w, int ignore_label, int* pan_out, int* label_out, uenc_stream_t stream);
+
 /* ---- launch timers (opt-in, process-global): per-launch HIP events on the launch stream ---------------- */
 int uenc_prof_enable(int on); /* also resets */
 int uenc_prof_collect(int kind /* 0 gemm_nt (128-tile, skinny), 1 gemm_tn*, 4 gemm_nt256, 5 gemm_nt128 */, double* ms_total, double* flops_total, long* launches);

@@ -162,6 +162,10 @@ _SIGNATURES = {
     "uenc_softmax_gate_bwd": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_p],
     "uenc_soft_att_depth_fwd": [c_p, c_i, c_p, c_p, c_l, c_i, c_p],
     "uenc_soft_att_depth_bwd": [c_p, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_p],
+    # training-time augmentation of one sample: windowed PIL resize + SSD colour, label gathers (csrc/augment.hip)
+    "uenc_augment_tile_fits": [c_i, c_i, c_i, c_i, c_i, c_i],
+    "uenc_augment_image": [c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
+    "uenc_augment_labels": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
 }
 
 

@@ -1713,3 +1713,56 @@ def soft_att_depth_bwd(ddisp: torch.Tensor, z: torch.Tensor, grid: torch.Tensor,
     check(lib.uenc_soft_att_depth_bwd(ddisp.data_ptr(), z.data_ptr(), dt(z), grid.data_ptr(), dz.data_ptr(), dt(dz), z.numel() // max(D, 1), D,
                                       stream_ptr()), "soft_att_depth_bwd")
     return dz
+
+
+# ---- training-time augmentation of one sample (csrc/augment.hip) ------------------------------------------------------------------------------
+AUG_TILE_W, AUG_TILE_H, AUG_MAX_TAPS, AUG_COLOUR_TAB_INTS = 64, 16, 7, 704
+
+
+def augment_tile_fits(in_h: int, in_w: int, rs_h: int, rs_w: int, kx: int, ky: int) -> bool:
+    """Whether one 64 x 16 output tile of the resize (in_h, in_w) -> (rs_h, rs_w) fits the image kernel's LDS.  No GPU is needed."""
+    return bool(lib.uenc_augment_tile_fits(int(in_h), int(in_w), int(rs_h), int(rs_w), int(kx), int(ky)))
+
+
+def _augment_geometry(plan):
+    (h, w), (rs_h, rs_w), (x0, y0, cw, ch), (out_h, out_w) = plan.src_hw, plan.resized_hw, plan.crop, plan.out_hw
+    return h, w, rs_h, rs_w, x0, y0, cw, ch, out_h, out_w
+
+
+def augment_image(buf: torch.Tensor, off: dict, meta: dict, plan) -> torch.Tensor:
+    """One launch on the current stream: the frames of one sample's upload `buf` (uint8, on the GPU; uenc.train_data.pack_plan wrote it:
+    tables, frames, panoptic PNG, label map at the byte offsets `off`) -> images (F, 3, H, W) uint8 under the sample's AugPlan.  A plan
+    whose tile does not fit the kernel's LDS is an error (UencError), there is no other path.  uenc_augment_image."""
+    _dev(buf, "buf", torch.uint8, 1)
+    h, w, rs_h, rs_w, x0, y0, cw, ch, out_h, out_w = _augment_geometry(plan)
+    base, F = buf.data_ptr(), int(meta["F"])
+    at = lambda name: base + off[name] if name in off else None
+    images = torch.empty((F, 3, out_h, out_w), dtype=torch.uint8, device=buf.device)
+    check(lib.uenc_augment_image(at("frame0"), int(meta["frame_stride"]), F, h, w, rs_h, rs_w, x0, y0, cw, ch, at("col_tab"), int(meta["kx"]),
+                                 at("row_tab"), int(meta["ky"]), at("colour_tab"), int(meta["flags"]), int(meta["hue"]), int(plan.flip),
+                                 out_h, out_w, int(plan.pad_image), images.data_ptr(), stream_ptr()), "augment_image")
+    return images
+
+
+def augment_labels(buf: torch.Tensor, off: dict, meta: dict, plan):
+    """One launch: the panoptic PNG and the label map of the upload -> (id map (H, W) int32, label map (H, W) int32 or None), or
+    (None, None) for an upload without a panoptic PNG.  uenc_augment_labels."""
+    _dev(buf, "buf", torch.uint8, 1)
+    if "pan" not in off:
+        return None, None
+    h, w, rs_h, rs_w, x0, y0, cw, ch, out_h, out_w = _augment_geometry(plan)
+    base = buf.data_ptr()
+    at = lambda name: base + off[name] if name in off else None
+    ids = torch.empty((out_h, out_w), dtype=torch.int32, device=buf.device)
+    lab = torch.empty((out_h, out_w), dtype=torch.int32, device=buf.device) if "label" in off else None
+    check(lib.uenc_augment_labels(at("pan"), at("label"), int(meta["label_bytes"]), h, w, rs_h, rs_w, x0, y0, cw, ch, at("pan_col"),
+                                  at("pan_row"), at("lab_col"), at("lab_row"), int(plan.flip), out_h, out_w, int(plan.pad_label),
+                                  ids.data_ptr(), ptr(lab), stream_ptr()), "augment_labels")
+    return ids, lab
+
+
+def augment_sample(buf: torch.Tensor, off: dict, meta: dict, plan):
+    """The two launches of one sample on the current stream, nothing copied back -> (images, id map or None, label map or None)."""
+    images = augment_image(buf, off, meta, plan)
+    ids, lab = augment_labels(buf, off, meta, plan)
+    return images, ids, lab
