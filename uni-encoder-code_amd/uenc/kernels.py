@@ -19,7 +19,8 @@ from .capi import BF16, F32, check, dt, lib, ptr, stream_ptr
 
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU = (
     capi.EPI_NONE, capi.EPI_GELU, capi.EPI_RELU, capi.EPI_RESIDUAL, capi.EPI_MUL_DGELU, capi.EPI_MUL_DRELU)
-NT_TILE_256X256, NT_TILE_256X192, NT_TILE_128X256 = 256, 192, 128       # UENC_NT_TILE_* of include/uenc.h (gemm_nt's `tile`)
+_H = capi.CONSTANTS             # the integer UENC_* macros of include/uenc.h: the constants of this module that mirror one are read from it
+NT_TILE_256X256, NT_TILE_256X192, NT_TILE_128X256 = (_H["UENC_NT_TILE_" + t] for t in ("256X256", "256X192", "128X256"))     # gemm_nt's `tile`
 
 
 # fp32 "exact" arithmetic mode (csrc/exact.hip): every activation that is bf16 between kernels in the
@@ -1212,7 +1213,7 @@ def crit_class_loss(call: CritCall, row_ind, col_ind, eos_coef: float):
 
 
 # ---- training targets from a panoptic id map (csrc/targets.hip) --------------------------------------------------------------------------------
-TARGETS_MAX_SEGMENTS = 256
+TARGETS_MAX_SEGMENTS = _H["UENC_TARGETS_MAX_SEGMENTS"]
 
 
 def _targets_table(pan, table, B):
@@ -1256,8 +1257,8 @@ def targets_write(pan: torch.Tensor, table: torch.Tensor, plan: torch.Tensor, to
 
 
 # ---- evaluation statistics on the device (csrc/evalstats.hip) ------------------------------------------------------------------------------------
-EVAL_MAX_CLASSES = 1024
-EVAL_PQ_DIM = TARGETS_MAX_SEGMENTS + 2          # VOID, 256 table rows, "unknown"
+EVAL_MAX_CLASSES = _H["UENC_EVAL_MAX_CLASSES"]
+EVAL_PQ_DIM = _H["UENC_EVAL_PQ_DIM"]            # TARGETS_MAX_SEGMENTS + 2: VOID, 256 table rows, "unknown"
 
 
 def eval_confusion(pred: torch.Tensor, gt: torch.Tensor, sizes: torch.Tensor, conf: torch.Tensor, ignore_label: int, max_blocks: int = 0):
@@ -1716,7 +1717,7 @@ def soft_att_depth_bwd(ddisp: torch.Tensor, z: torch.Tensor, grid: torch.Tensor,
 
 
 # ---- training-time augmentation of one sample (csrc/augment.hip) ------------------------------------------------------------------------------
-AUG_TILE_W, AUG_TILE_H, AUG_MAX_TAPS, AUG_COLOUR_TAB_INTS = 64, 16, 7, 704
+AUG_TILE_W, AUG_TILE_H, AUG_MAX_TAPS, AUG_COLOUR_TAB_INTS = (_H["UENC_AUG_" + n] for n in ("TILE_W", "TILE_H", "MAX_TAPS", "COLOUR_TAB_INTS"))
 
 
 def augment_tile_fits(in_h: int, in_w: int, rs_h: int, rs_w: int, kx: int, ky: int) -> bool:
