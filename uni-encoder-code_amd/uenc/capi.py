@@ -7,6 +7,9 @@ nothing and never synchronises.  Return convention: 0 ok, <0 invalid argument (n
 The binding is derived from the header when this module is imported: `parse_header()` reads every declaration and every integer
 `#define UENC_*` of include/uenc.h, and `_load()` sets each function's `argtypes` / `restype` from that.  So a new entry point or
 constant is declared in include/uenc.h and nowhere else; a type the parser's table does not list is an error, never a guess.
+
+include/uenc.h is the frozen core ABI (`FUNCTIONS`, `CONSTANTS`, `exported_symbols()`).  Entry points added since are declared in
+include/uenc_ext.h, defined under csrc/ext/ and bound here on the same `lib` as `EXT_FUNCTIONS` / `EXT_CONSTANTS`.
 """
 import ctypes
 import os
@@ -17,6 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libuenc_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "uenc.h"))
+EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "uenc_ext.h"))
 
 # the C types of the header's parameters and results; anything with a `*` is a pointer
 _CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "int64_t": ctypes.c_long, "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint,
@@ -40,6 +44,7 @@ def parse_header(text):
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants = {m[1]: int(m[2], 0) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(UENC_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", text, re.M)}
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'\bextern\s+"C"\s*\{', " ", text)          # uenc_ext.h has no typedef between the brace and its first declaration
     functions = {}
     for stmt in text.split(";"):
         if "(" not in stmt:             # the typedef, the braces of extern "C"
@@ -58,6 +63,13 @@ class UencError(RuntimeError):
     pass
 
 
+def _bind(lib, functions):
+    for name, (restype, argtypes) in functions.items():
+        fn = getattr(lib, name)          # AttributeError if the library and the header drift apart
+        fn.argtypes = argtypes
+        fn.restype = restype
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -69,14 +81,23 @@ def _load():
     except OSError as e:
         raise ImportError(f"{HEADER_PATH} cannot be read ({e}): the binding is derived from it, the package is used in-tree") from e
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in functions.items():
-        fn = getattr(lib, name)          # AttributeError if the library and the header drift apart
-        fn.argtypes = argtypes
-        fn.restype = restype
+    _bind(lib, functions)
     return lib, functions, constants
 
 
+def _load_ext(lib):
+    """The extension header, after the core one: same parser, same library object.  Its names stay out of FUNCTIONS / CONSTANTS."""
+    try:
+        with open(EXT_HEADER_PATH) as f:
+            functions, constants = parse_header(f.read())
+    except OSError as e:
+        raise ImportError(f"{EXT_HEADER_PATH} cannot be read ({e}): the binding of the extension entry points is derived from it") from e
+    _bind(lib, functions)
+    return functions, constants
+
+
 lib, FUNCTIONS, CONSTANTS = _load()
+EXT_FUNCTIONS, EXT_CONSTANTS = _load_ext(lib)
 
 F32, BF16 = CONSTANTS["UENC_F32"], CONSTANTS["UENC_BF16"]
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU = (

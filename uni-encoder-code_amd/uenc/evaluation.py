@@ -13,7 +13,9 @@ tests/golden/data_eval.npz, tests/test_data_eval_cpu.py).
 The two segmentation evaluators of the reference's driver (train_net.py:94-108) score here without a third-party package and, with
 accumulate="device", without leaving the GPU until `evaluate()` (csrc/evalstats.hip): `SemSegEvaluator` and `PanopticEvaluator` /
 `COCOPanopticEvaluator`; `build_evaluator` picks them as the reference's Trainer does.  Everything they count is an integer, so the
-host and the device paths agree exactly.
+host and the device paths agree exactly.  The two depth evaluators take accumulate="device" as well (csrc/ext/depth_eval.hip): they score
+every image where the model left its disparity and keep one row of doubles per image on the device; their two paths agree to about 1e-5
+relative (the prediction is rounded to fp32 on either path, differently), not bit for bit.
 
 Panoptic quality: the rules of panopticapi's `pq_compute_single_core` and `PQStat.pq_average`, which `pq_match_host`,
 uenc_eval_pq_match and `PanopticEvaluator.evaluate` implement literally.  Per image, inter[g, p] = the pixels that have ground-truth id g
@@ -489,23 +491,61 @@ class _DepthEvaluator(DatasetEvaluator):
     """Shared protocol of the two depth evaluators: process() collects (ground-truth depth map, prediction) pairs, evaluate() scores
     every image after median scaling and averages the seven metrics over images -> {"depth_error": {...}} on the main process.
     (The reference parks the pairs as .npy files in a temporary directory shared by the ranks of one machine; here they stay in
-    memory and are gathered.)"""
+    memory and are gathered.)
+    accumulate="device": process() scores every image where the model left its disparity (csrc/ext/depth_eval.hip: resize + invert,
+    valid mask, exact medians, the seven sums), uploads only the ground truth, keeps one row of doubles per image on the device, copies
+    nothing back and does not synchronise; evaluate() reads the rows once.  The device path rounds the prediction to fp32 once (the host
+    path resizes in fp32 as well, with fp32 weights) and sums in fp64: the two agree to about 1e-5 relative, not bit for bit."""
     MIN_DEPTH = 1e-3
     MAX_DEPTH = 80
 
-    def __init__(self, dataset_name=None):
+    ROW_CHUNK = 256                # rows the device buffer grows by
+
+    def __init__(self, dataset_name=None, accumulate: str = "host"):
         self._dataset_name = dataset_name
+        self._accumulate = _check_accumulate(accumulate)
         self._logger = logging.getLogger(__name__)
-        self._pairs = []
+        self.reset()
 
     def reset(self):
         self._pairs = []
+        self._dev_rows, self._dev_count, self._dev_ws = None, 0, {}       # (capacity, DEPTH_EVAL_ROW) fp64 on the device, rows in use
+
+    def _score_device(self, depth_gt: np.ndarray, disp: torch.Tensor, window):
+        """One image on the device: depth_gt (H, W) host fp32 / fp64 (uploaded as it is), disp (h, w) the scaled disparity where the model
+        left it, window = (r0, r1, c0, c1) computed by the caller exactly as the host path slices.  Appends one row; copies nothing
+        back and does not synchronise (growing the buffer allocates)."""
+        from . import kernels as K
+        if depth_gt.dtype not in (np.float32, np.float64):
+            depth_gt = depth_gt.astype(np.float64)
+        gt = torch.from_numpy(np.ascontiguousarray(depth_gt)).to(disp.device)
+        H, W = gt.shape
+        i = self._dev_count
+        if self._dev_rows is None or i >= self._dev_rows.shape[0]:
+            grown = torch.zeros((i + self.ROW_CHUNK, K.DEPTH_EVAL_ROW), dtype=torch.float64, device=disp.device)
+            if self._dev_rows is not None:
+                grown[:i] = self._dev_rows
+            self._dev_rows = grown
+        r0, r1, c0, c1 = (int(v) for v in window)
+        r0, r1, c0, c1 = min(max(r0, 0), H), min(max(r1, 0), H), min(max(c0, 0), W), min(max(c1, 0), W)      # as a slice clamps
+        if r0 >= r1 or c0 >= c1:                                            # an empty window scores like an empty valid set
+            self._dev_rows[i] = float("nan")
+            self._dev_rows[i, 7] = 0.0
+        else:
+            key = (H, W, disp.device)
+            if key not in self._dev_ws:
+                self._dev_ws[key] = K.depth_eval_ws(H, W, disp.device)
+            pred = K.depth_eval_pred(disp.detach().float().contiguous(), (H, W))
+            K.depth_eval_score(gt, pred, (r0, r1, c0, c1), self.MIN_DEPTH, self.MAX_DEPTH, self._dev_rows, i, self._dev_ws[key])
+        self._dev_count = i + 1
 
     def _score(self, depth_gt: np.ndarray, pred: np.ndarray):
         raise NotImplementedError
 
     def evaluate(self):
         import torch.distributed as dist
+        if self._accumulate == "device":
+            return self._evaluate_device()
         pairs = self._pairs
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             box = [None] * dist.get_world_size()
@@ -515,6 +555,21 @@ class _DepthEvaluator(DatasetEvaluator):
             return None
         rows = [self._score(gt, pred) for gt, pred in pairs]
         means = np.mean(np.asarray(rows, dtype=np.float64), axis=0) if rows else np.full(7, np.nan)
+        return OrderedDict(depth_error={k: v for k, v in zip(_DEPTH_KEYS, means)})
+
+    def _evaluate_device(self):
+        """The one read-back: the seven metrics of every image; several ranks gather these rows, not maps."""
+        import torch.distributed as dist
+        rows = np.zeros((0, 7), dtype=np.float64)
+        if self._dev_rows is not None and self._dev_count:
+            rows = self._dev_rows[:self._dev_count, :7].cpu().numpy()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            box = [None] * dist.get_world_size()
+            dist.all_gather_object(box, rows)
+            rows = np.concatenate(box, axis=0)
+        if not _is_main_process():
+            return None
+        means = np.mean(rows, axis=0) if len(rows) else np.full(7, np.nan)
         return OrderedDict(depth_error={k: v for k, v in zip(_DEPTH_KEYS, means)})
 
     def _scaled_errors(self, depth_gt: np.ndarray, depth_pred: np.ndarray):
@@ -584,17 +639,29 @@ class KITTIDepthEvaluator(_DepthEvaluator):
         depth[depth < 0] = 0
         return depth
 
+    @staticmethod
+    def _eigen_crop(h: int, w: int):
+        return np.array([0.40810811 * h, 0.99189189 * h, 0.03594771 * w, 0.96405229 * w]).astype(np.int32)
+
     def process(self, inputs, outputs):
         for inp, out in zip(inputs, outputs):
+            if self._accumulate == "device":
+                _need_device(out["disp_results"], 'out["disp_results"]')
             depth_gt = self.generate_depth_map(inp["calib_path"], inp["velo_file"], 2, True)
             disp, _ = disp_to_depth(out["disp_results"])
+            if self._accumulate == "device":
+                disp = disp.squeeze()
+                if disp.dim() != 2:
+                    raise ValueError(f'out["disp_results"] must hold one (h, w) map, got {tuple(out["disp_results"].shape)}')
+                self._score_device(depth_gt, disp, self._eigen_crop(*depth_gt.shape[:2]))
+                continue
             disp = np.asarray(disp.squeeze().detach().float().cpu().numpy())
             self._pairs.append((depth_gt, 1 / _resize_bilinear(disp, depth_gt.shape[1], depth_gt.shape[0])))
 
     def _score(self, depth_gt, depth_pred):
         h, w = depth_gt.shape[:2]
         mask = np.logical_and(depth_gt > self.MIN_DEPTH, depth_gt < self.MAX_DEPTH)
-        crop = np.array([0.40810811 * h, 0.99189189 * h, 0.03594771 * w, 0.96405229 * w]).astype(np.int32)      # Eigen crop
+        crop = self._eigen_crop(h, w)
         inside = np.zeros(mask.shape, dtype=bool)
         inside[crop[0]:crop[1], crop[2]:crop[3]] = True
         mask &= inside
@@ -609,6 +676,15 @@ class CityscapesDepthEvaluator(_DepthEvaluator):
     def process(self, inputs, outputs):
         for inp, out in zip(inputs, outputs):
             gt_path = inp["file_name"].replace("/leftImg8bit/test/", "/gt_depths/").replace(".png", ".npy")
+            if self._accumulate == "device":
+                _need_device(out["disp_results"], 'out["disp_results"]')
+                disp, _ = disp_to_depth(out["disp_results"])
+                depth_gt = np.load(gt_path)                                 # once per call, not per batch element
+                h, w = depth_gt.shape[:2]
+                h = int(round(h * 0.75))
+                for d in disp[:, 0]:
+                    self._score_device(depth_gt[:h], d, (256, h, 192, 1856))
+                continue
             disp, _ = disp_to_depth(out["disp_results"])
             for d in disp.detach().float().cpu()[:, 0].numpy():
                 self._pairs.append((np.load(gt_path), d))
@@ -654,7 +730,8 @@ CityscapesSemSegEvaluator = _needs("CityscapesSemSegEvaluator", "cityscapesscrip
 
 def build_evaluator(cfg, dataset_name: str, accumulate: str = "device", output_folder: Optional[str] = None):
     """The reference's Trainer.build_evaluator (train_net.py:75-149): the evaluator(s) for a dataset by its metadata's `evaluator_type`
-    and cfg.MODEL.TEST.  The segmentation evaluators count on the device by default.  The branches whose scorers are third-party packages
+    and cfg.MODEL.TEST.  `accumulate` goes to the segmentation evaluators and to both depth evaluators: they count / score on the device
+    by default.  The branches whose scorers are third-party packages
     (Cityscapes instance / semantic scripts, COCO instance AP) construct the names that raise."""
     from .data import MetadataCatalog
     meta = MetadataCatalog.get(dataset_name)
@@ -664,7 +741,7 @@ def build_evaluator(cfg, dataset_name: str, accumulate: str = "device", output_f
     test = cfg.MODEL.TEST
     evaluators = []
     if evaluator_type == "kitti_depth" and test.DEPTH_ON:
-        evaluators.append(KITTIDepthEvaluator(dataset_name))
+        evaluators.append(KITTIDepthEvaluator(dataset_name, accumulate=accumulate))
     if evaluator_type in ("sem_seg", "ade20k_panoptic_seg"):
         evaluators.append(SemSegEvaluator(len(meta.stuff_classes), ignore_label=getattr(meta, "ignore_label", 255), accumulate=accumulate))
     if evaluator_type in ("coco_panoptic_seg", "ade20k_panoptic_seg", "cityscapes_panoptic_seg", "mapillary_vistas_panoptic_seg") and test.PANOPTIC_ON:
@@ -679,7 +756,7 @@ def build_evaluator(cfg, dataset_name: str, accumulate: str = "device", output_f
         if test.INSTANCE_ON:
             evaluators.append(CityscapesInstanceEvaluator(dataset_name))
     if evaluator_type == "cityscapes_depth" and test.DEPTH_ON:
-        evaluators.append(CityscapesDepthEvaluator(dataset_name))
+        evaluators.append(CityscapesDepthEvaluator(dataset_name, accumulate=accumulate))
     if evaluator_type == "ade20k_panoptic_seg" and test.INSTANCE_ON:
         evaluators.append(InstanceSegEvaluator(dataset_name, output_dir=output_folder))
     if not evaluators:

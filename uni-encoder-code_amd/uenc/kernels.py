@@ -1330,6 +1330,52 @@ def eval_pq_unpack(out, B: int, num_categories: int):
     return out[:a].reshape(B, S, 4), out[a:b].reshape(B, K), out[b:c].reshape(B, K), out[c:]
 
 
+# ---- depth evaluation on the device (csrc/ext/depth_eval.hip; declared in include/uenc_ext.h) ---------------------------------------------------
+_X = capi.EXT_CONSTANTS
+DEPTH_EVAL_ROW = _X["UENC_DEPTH_EVAL_ROW"]      # doubles per image: the seven metrics, n, median gt, median pred, the three threshold counts
+DEPTH_EVAL_LAUNCHES = {torch.float32: _X["UENC_DEPTH_EVAL_LAUNCHES_F32"], torch.float64: _X["UENC_DEPTH_EVAL_LAUNCHES_F64"]}   # kernels of one score
+_DEPTH_GT = {torch.float32: F32, torch.float64: _X["UENC_EXT_F64"]}
+
+
+def depth_eval_pred(disp: torch.Tensor, size, want_resized: bool = False):
+    """disp (h, w) fp32, a scaled disparity -> pred (H, W) fp32 = 1 / bilinear resize to size = (H, W) (half-pixel centres, taps and
+    lerps in fp64, one rounding); with want_resized also the resized disparity.  uenc_depth_eval_pred."""
+    _dev(disp, "disp", torch.float32, 2)
+    H, W = int(size[0]), int(size[1])
+    pred = torch.empty((H, W), dtype=torch.float32, device=disp.device)
+    resized = torch.empty_like(pred) if want_resized else None
+    check(lib.uenc_depth_eval_pred(disp.data_ptr(), pred.data_ptr(), ptr(resized), int(disp.shape[0]), int(disp.shape[1]), H, W, stream_ptr()),
+          "depth_eval_pred")
+    return (pred, resized) if want_resized else pred
+
+
+def depth_eval_ws(H: int, W: int, device) -> torch.Tensor:
+    """The workspace `depth_eval_score` needs for (H, W) maps.  uenc_depth_eval_ws_bytes."""
+    n = lib.uenc_depth_eval_ws_bytes(int(H), int(W))
+    if n < 0:
+        raise capi.UencError(f"depth_eval_ws: a map of {H} x {W} is refused")
+    return torch.empty((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def depth_eval_score(gt: torch.Tensor, pred: torch.Tensor, window, min_depth: float, max_depth: float, rows: torch.Tensor, row: int,
+                     ws: Optional[torch.Tensor] = None):
+    """rows[row] <- the score of one image: gt (H, W) fp32 or fp64, pred (H, W) fp32, window = (r0, r1, c0, c1), rows
+    (capacity, DEPTH_EVAL_ROW) fp64.  Nothing is copied back.  uenc_depth_eval_score."""
+    if gt.dtype not in _DEPTH_GT:
+        raise capi.UencError(f"depth_eval_score: gt must be float32 or float64, got {gt.dtype}")
+    _dev(gt, "gt", gt.dtype, 2); _dev(pred, "pred", torch.float32, 2); _dev(rows, "rows", torch.float64, 2)
+    H, W = gt.shape
+    if tuple(pred.shape) != (H, W) or rows.shape[1] != DEPTH_EVAL_ROW:
+        raise capi.UencError(f"depth_eval_score: gt {tuple(gt.shape)}, pred {tuple(pred.shape)}, rows {tuple(rows.shape)} do not fit")
+    if ws is None:
+        ws = depth_eval_ws(H, W, gt.device)
+    r0, r1, c0, c1 = (int(v) for v in window)
+    check(lib.uenc_depth_eval_score(gt.data_ptr(), _DEPTH_GT[gt.dtype], pred.data_ptr(), H, W, r0, r1, c0, c1, float(min_depth), float(max_depth),
+                                    ws.data_ptr(), ws.numel() * 8, rows.data_ptr(), int(row), int(rows.shape[0]), stream_ptr()),
+          "depth_eval_score")
+    return rows
+
+
 # ---- MonodepthLoss: view synthesis + photometric loss (csrc/monodepth.hip) -----------------------------------------------------------------
 # slots of the 67-pointer descriptor of uenc_view_synth_fwd / _bwd (struct VsDesc)
 _VS = {"disp": 0, "cflow": 4, "mask": 12, "T": 20, "K": 21, "invK": 22, "src": 23, "color": 24, "sample": 25, "sample_ego": 26, "sample_cmp": 27,
