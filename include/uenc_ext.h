@@ -42,6 +42,12 @@ int uenc_depth_eval_score(const void* gt, int gt_dtype, const float* pred, int H
                           double min_depth, double max_depth, void* ws, long ws_bytes, double* rows, int row, int capacity,
                           uenc_stream_t stream);
 
+/* ---- neighbourhood attention: what the planner of uenc_na2d_fwd / uenc_na2d_bwd decides (csrc/ext/na2d_plan.hip; host code only) ----
+ * The number of consecutive tiles of a residue class one workgroup of the matrix-core kernels walks for this problem, 0 where the
+ * VALU kernels run instead (K >= 9, or a per-image qkv extent of 2^31 elements or more), < 0 for arguments uenc_na2d_fwd refuses.
+ * Nothing is launched.  tests/na2d_cases.py restates the planner and is held against this. */
+int uenc_na2d_tiles_per_group(int B, int H, int W, int nH, int K, int dilation);
+
 #ifdef __cplusplus
 }
 #endif

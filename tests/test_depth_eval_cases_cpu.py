@@ -27,7 +27,7 @@ def test_ext_declarations_are_exported_and_bound_as_parsed():
     from uenc import capi
     with open(EXT_HEADER) as f:
         functions, constants = capi.parse_header(f.read())
-    assert sorted(functions) == ["uenc_depth_eval_pred", "uenc_depth_eval_score", "uenc_depth_eval_ws_bytes"]
+    assert sorted(functions) == ["uenc_depth_eval_pred", "uenc_depth_eval_score", "uenc_depth_eval_ws_bytes", "uenc_na2d_tiles_per_group"]
     assert functions == capi.EXT_FUNCTIONS and constants == capi.EXT_CONSTANTS
     for name, (restype, argtypes) in functions.items():
         fn = getattr(capi.lib, name)
@@ -35,6 +35,7 @@ def test_ext_declarations_are_exported_and_bound_as_parsed():
     c = ctypes
     assert functions["uenc_depth_eval_ws_bytes"] == (c.c_long, [c.c_int, c.c_int])
     assert functions["uenc_depth_eval_score"][1][9:11] == [c.c_double, c.c_double]
+    assert functions["uenc_na2d_tiles_per_group"] == (c.c_int, [c.c_int] * 6)         # csrc/ext/na2d_plan.hip (tests/test_na2d_cases_cpu.py)
     assert constants["UENC_DEPTH_EVAL_ROW"] == 13 and constants["UENC_EXT_F64"] not in (capi.F32, capi.BF16)
 
 

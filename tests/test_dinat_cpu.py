@@ -8,32 +8,8 @@ import pytest
 from oracle import dinat_ref as D
 
 
-def natten_window_start(index, length, K, NS, d):
-    """NATTEN 0.14.4 get_window_start, restated literally (scalar)."""
-    if d <= 1:
-        return max(index - NS, 0) + (index + NS >= length) * (length - index - NS - 1)
-    ni = index - NS * d
-    if ni < 0:
-        return index % d
-    if index + NS * d >= length:
-        imodd = index % d
-        a = (length // d) * d
-        b = length - a
-        if imodd < b:
-            return length - b + imodd - 2 * NS * d
-        return a + imodd - K * d
-    return ni
-
-
-def natten_pb_start(index, length, K, NS, d):
-    """NATTEN 0.14.4 get_pb_start, restated literally (scalar)."""
-    if d <= 1:
-        return NS + (index < NS) * (NS - index) + (index + NS >= length) * (length - index - 1 - NS)
-    if index - NS * d < 0:
-        return K - 1 - (index // d)
-    if index + NS * d >= length:
-        return (length - index - 1) // d
-    return NS
+# NATTEN 0.14.4's get_window_start / get_pb_start, restated literally: tests/na2d_cases.py holds them (its float64 reference is built on them)
+from na2d_cases import natten_pb_start, natten_window_start  # noqa: E402
 
 
 @pytest.mark.parametrize("length,k,d", [(7, 7, 1), (16, 7, 1), (23, 7, 2), (29, 7, 3), (21, 3, 4), (40, 5, 7), (26, 13, 2), (64, 7, 8)])

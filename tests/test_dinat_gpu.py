@@ -7,7 +7,15 @@ fixtures in the reference); the oracle restates NATTEN's published algorithm and
 Tolerances (relative L2 error): kernels read bf16 q / k / v and write bf16 outputs and gradients (2^-9 relative rounding each),
 softmax and accumulation in fp32 -> rel <= 1e-2 for the attention output, 2e-2 for its gradients; whole backbone: rel <= 3e-2 on
 the stage features (the Swin path's 1.5e-2 plus one bf16-operand 3x3 convolution over a 9C-long contraction per stage, each
-feeding a LayerNorm), 8e-2 on parameter gradients (as for the full Swin model)."""
+feeding a LayerNorm), 8e-2 on parameter gradients (as for the full Swin model).
+
+Pinned element-wise elsewhere: tests/test_na2d_kernels_gpu.py holds every element of out, lse, dq, dk, dv and drpb of `uenc_na2d_fwd` /
+`uenc_na2d_bwd` (and of the fp32 twins `uenc_na2d_f32_*`) against a float64 reference with per-element bars (tests/na2d_cases.py), at the
+shapes where the planner gives a workgroup several tiles (nt = 2, 3, 8 -- every parametrisation below has at most 216 tiles, nt == 1), at
+the largest per-key LDS image, the full 20 x 28 VALU halo, NULL rpb / drpb / lse, and each image of a batch against the image alone, bit
+for bit.  That reference is a second, independent statement of NATTEN's published definition (get_window_start / get_pb_start restated
+literally, float64 autograd), not NATTEN's output: NATTEN itself is still absent, so against NATTEN this remains parity unpinned (PARITY
+UNPINNED above).  The tests and bars of this file are as they were."""
 import pytest
 import torch
 

@@ -35,3 +35,6 @@ static int na2d_check(const Na2d& p, int K) {
 int na2d_mfma_fwd(const Na2d& p, int K, hipStream_t stream);
 int na2d_mfma_bwd(Na2d& p, int K, hipStream_t stream);
 bool na2d_mfma_supported(int H, int W, int nH, int K);
+// the MFMA kernels' schedule: tiles per residue class, consecutive tiles per workgroup (nt), workgroups per class (chunks)
+struct NmPlan { int tiles_x, tiles_y, nt, chunks; };
+NmPlan na2d_mfma_plan(int B, int H, int W, int nH, int d);

@@ -580,18 +580,29 @@ __global__ __launch_bounds__(512) void na2d_mfma_bwd_kv_kernel(Na2d p) {
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------------------
-static dim3 nm_plan(Na2d& p) {
-    const int Lx = (p.W + p.d - 1) / p.d, Ly = (p.H + p.d - 1) / p.d;      // the longest residue class
-    p.tiles_x = (Lx + NM_TW - 1) / NM_TW; p.tiles_y = (Ly + NM_TH - 1) / NM_TH;
-    p.inv_tiles_x = 1.0f / (float)p.tiles_x;
-    const int per_class = p.tiles_x * p.tiles_y;
-    const long total = (long)per_class * p.d * p.d * p.B * p.nH;
+// The one place that holds the planner's arithmetic: both launchers go through nm_plan below, and uenc_na2d_tiles_per_group
+// (csrc/ext/na2d_plan.hip) reports its nt to the tests.
+NmPlan na2d_mfma_plan(int B, int H, int W, int nH, int d) {
+    NmPlan q;
+    const int Lx = (W + d - 1) / d, Ly = (H + d - 1) / d;      // the longest residue class
+    q.tiles_x = (Lx + NM_TW - 1) / NM_TW; q.tiles_y = (Ly + NM_TH - 1) / NM_TH;
+    const int per_class = q.tiles_x * q.tiles_y;
+    const long total = (long)per_class * d * d * B * nH;
     // tiles per workgroup: enough workgroups for ~6 per CU, at most 8 tiles each, never more than a class has
     int nt = (int)(total / 1536);
     nt = nt < 1 ? 1 : (nt > 8 ? 8 : nt);
     if (nt > per_class) nt = per_class;
-    p.nt = nt;
-    return dim3((per_class + nt - 1) / nt, p.d * p.d, p.B * p.nH);
+    q.nt = nt;
+    q.chunks = (per_class + nt - 1) / nt;
+    return q;
+}
+
+static dim3 nm_plan(Na2d& p) {
+    const NmPlan q = na2d_mfma_plan(p.B, p.H, p.W, p.nH, p.d);
+    p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y;
+    p.inv_tiles_x = 1.0f / (float)p.tiles_x;
+    p.nt = q.nt;
+    return dim3(q.chunks, p.d * p.d, p.B * p.nH);
 }
 
 int na2d_mfma_fwd(const Na2d& p0, int K, hipStream_t stream) {
